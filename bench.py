@@ -23,6 +23,13 @@ planted effects or the cross-validation does not select the planted model size.
 and relays rank 0's line; started under a launcher (WORLD_SIZE set) it is one of the ranks.  `--mode replicas` keeps round 1's
 independent replicas of configs[2] (weak scaling, no exchange).
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps (with the roofline's HIP events), the outputs if
+`--dump-outputs DIR` is given, the line.  Everything else above -- the host-driven A/B, the steps with the measurement hook off,
+the recovery check, `cv_iht`, `mv`, `dense`, `cpu_baseline` and `cpu_baseline_cv` -- runs with `--full` (the `--no-*` options
+leave out parts of it).  `--dump-outputs DIR` writes what the caller of the timed session holds after its last step: the model
+(beta.npy, c.npy) and the last step's loglikelihood, tolerance and the timed steps' backtracks, all float64; the inputs are
+seeded, so two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).  The CPU baselines are a port (the repo's oracle), not MendelIHT.jl: no Julia here.
 """
 import argparse
@@ -69,7 +76,28 @@ def parse():
     ap.add_argument("--cv-steps", type=int, default=2, help="timed whole cross-validations of the secondary object at N>1")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per X'r launch from a separate rocprofv3 --pmc pass (corrected)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the same-box diagnostics, the recovery check and the secondary objects (cv_iht, mv, dense, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed session computed in its last step as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20        # --dump-outputs writes at most this much
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy in float64 for every array; a vector too large for the budget is replaced by a fixed, seeded sample of its
+    entries (sorted positions in <name>_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {name: np.asarray(v, dtype=np.float64).ravel() for name, v in arrays.items()}
+    room = DUMP_BUDGET_BYTES - 4096 - sum(v.nbytes for name, v in arrays.items() if name != "beta")     # (4096: the .npy headers)
+    beta = arrays["beta"]
+    if beta.nbytes > room:                                  # a sample costs 16 bytes an entry: the value and its position
+        idx = np.sort(np.random.default_rng(0).choice(beta.size, size=room // 16, replace=False))
+        arrays["beta"], arrays["beta_index"] = beta[idx], idx.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), v)
 
 
 def host_cpus():
@@ -432,6 +460,8 @@ def main():
         a.steps = 100
     if a.warmup is None:
         a.warmup = 5
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
     import torch
     import torch.distributed as dist
 
@@ -533,7 +563,7 @@ def main():
     # (round 6: BEFORE the timed session exists -- beside a resident session that has just run, and later in the process when the chip
     # is warmer, the same steps measured 0.46-0.69 ms outside the pass instead of 0.30-0.33: tools/coexist_probe.py)
     ab = None
-    if world == 1 and a.step_mode == 0:
+    if a.full and world == 1 and a.step_mode == 0:
         s2 = m.IHTSession(y, x, None, k=k, d=m.Normal(), l=m.IdentityLink(), step_mode=1)
         for _ in range(a.warmup):
             s2.step()
@@ -573,12 +603,22 @@ def main():
     step_counters = m.profile_counters(x, reset=True)
     exch = m.profile_exchange(x, reset=True)
     comm_info = comm.info() if (comm is not None and hasattr(comm, "info")) else None
+    if a.dump_outputs:
+        # what the caller of the timed session holds after its last step, read before anything else runs on the session; at N > 1
+        # every rank's block of beta goes to its own columns of the full-length vector (the other entries are zero: the sum is exact)
+        bl, cl = sess.model()
+        if sharded:
+            full_beta = np.zeros(p)
+            full_beta[lo:lo + cnt] = bl
+            bl = sum_over_ranks(full_beta)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"beta": bl, "c": cl, "logl": [logl], "tol": [tol], "backtracks": [nbt]})
 
     # ... and of what the measurement itself costs (N = 1): the same session goes on for a few steps with the hook OFF.  The hook
     # brackets every X'r pass with two HIP event records, queue operations of their own inside the step chain; the timed region
     # above carries them (the roofline is measured there), this figure says what a step takes without them
     unhooked = None
-    if world == 1:
+    if a.full and world == 1:
         nun = min(a.steps, 20)
         # the pass kernel's duration beside these steps: 20 hooked steps first (the chip is warmer than in the timed region, and the
         # kernel slower by 0.1-0.2 ms: subtracting the timed region's figure charged that to the chain)
@@ -599,15 +639,17 @@ def main():
                             "duration is that of 20 hooked steps run right before (the same temperature)"}
     #  the model is read AFTER the continuation (reading it brings the iterate home and the chain would have to warm up again):
     # true_effects_recovered describes the iterate whose loglikelihood is without_the_measurement_hook.logl_after_these_steps
-    bhat, _ = sess.model()
-    found = float(np.intersect1d(np.flatnonzero(bhat) + lo, supp).size)
-    recovered = int(sum_over_ranks([found])[0]) if sharded else int(found)
+    recovered = None
+    if a.full:
+        bhat, _ = sess.model()
+        found = float(np.intersect1d(np.flatnonzero(bhat) + lo, supp).size)
+        recovered = int(sum_over_ranks([found])[0]) if sharded else int(found)
 
     sess.close()
     del sess                                                # (it holds a reference to the matrix: the shard must be gone before the full replica comes)
     # ---- secondary at N > 1: BASELINE configs[4] column-sharded over the same ranks, through the same communicator ----------
     mv_sharded = None
-    if sharded and comm is not None and not a.no_mv:
+    if a.full and sharded and comm is not None and not a.no_mv:
         try:
             mv_sharded = mv_object(m, x, n, p, torch, comm=comm, lo=lo, sum_over_ranks=sum_over_ranks)
         except Exception as e:      # noqa: BLE001 -- reported in the line, the headline stands
@@ -654,7 +696,7 @@ def main():
                                    + (f": ONE fit, SNP columns sharded over {world} GPUs" if sharded else "")
                                    + (", one independent replica per GPU" if mode == "replicas" and world > 1 else ""),
                        "n": n, "p": p, "k": k, "xtv_variant": a.variant, "generator_s": round(t_gen, 2),
-                       "backtracks_in_timed_steps": nbt, "true_effects_recovered": f"{recovered}/{k}",
+                       "backtracks_in_timed_steps": nbt,
                        "final_logl": logl, "host_small_kernels_and_exchange_ms_per_step": 1e3 * elapsed / a.steps - kern_ms,
                        "step_mode": ("0: iht_one_step! resident on the device -- iterate, top-k finish, backtracking decision in device "
                                      "memory, the kernels of a step queued without a host wait" if a.step_mode == 0 and not sharded else
@@ -690,12 +732,14 @@ def main():
                                        "durations pooled over the launches of all ranks")
             out["per_rank"] = [{"rank": i, "columns": int(r[3]), "xtv_launches": int(r[0]), "xtv_kernel_ms": r[1] / max(r[0], 1),
                                 "xtv_GBps": r[2] / max(r[1], 1e-9) / 1e6} for i, r in enumerate(rows)]
-        if mode != "replicas" and recovered < 0.99 * k:
-            failures.append(f"the fit recovered {recovered} of {k} planted effects (< 99 %)")
+        if recovered is not None:
+            out["config"]["true_effects_recovered"] = f"{recovered}/{k}"
+            if mode != "replicas" and recovered < 0.99 * k:
+                failures.append(f"the fit recovered {recovered} of {k} planted effects (< 99 %)")
 
     # ---- secondary: BASELINE configs[3] on full replicas of X (the path's natural shard), with its own one-GPU reference ----
     gpu_fits_per_s = None
-    run_cv = mode == "fit" and not a.no_cv
+    run_cv = a.full and mode == "fit" and not a.no_cv
     if run_cv and one_device and world > 1:
         _free, tot = torch.cuda.mem_get_info()
         if world * (p * ((n + 3) // 4)) * 1.3 > tot:             # the ranks share ONE device: full replicas may not fit beside each other
@@ -809,18 +853,18 @@ def main():
                 if not same:
                     failures.append("the losses of the sharded cross-validation differ from the one-GPU run")
     # ---- secondary: BASELINE configs[4] (N = 1): MvNormal, r = 10 traits, k = 500 on the same matrix ------------------------
-    if world == 1 and mode == "fit" and not a.no_mv and (n, p) == (500_000, 1_000_000):
+    if a.full and world == 1 and mode == "fit" and not a.no_mv and (n, p) == (500_000, 1_000_000):
         out["mv"] = mv_object(m, x, n, p, torch)
     elif rank == 0 and mv_sharded is not None:
         out["mv"] = mv_sharded
     # ---- secondary: BASELINE configs[1] (N = 1): the dense Matrix{Float64} pass, randn(50000, 100000) --------------------------
-    if world == 1 and mode == "fit" and not a.no_dense and (n, p) == (500_000, 1_000_000):
+    if a.full and world == 1 and mode == "fit" and not a.no_dense and (n, p) == (500_000, 1_000_000):
         try:
             out["dense"] = dense_object(m, torch)
         except Exception as e:      # noqa: BLE001 -- reported in the line, the headline stands
             out["dense"] = {"error": repr(e)}
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"], cores = cpu_baseline(m, n, p, k, seed, a.cpu_seconds)
             if gpu_fits_per_s is not None:
                 out["cpu_baseline_cv"] = cpu_baseline_cv(m, n, p, seed, cores, gpu_fits_per_s)

@@ -1,7 +1,7 @@
 """Per-step view of a rocprofv3 --kernel-trace of bench.py: the kernels between two X'r passes, in order, with durations and gaps.
 usage: python tools/trace_chain.py <dir with *_kernel_trace.csv> [steps to show] [resident|host|any]
 `resident` (default) shows steps of the device-resident chain (those with a k_res_decide in them), `host` the host-driven ones
-(bench.py's same-box A/B runs them after the timed region), `any` the last ones of the trace whatever they are."""
+(the same-box A/B of `bench.py --full` runs them before the timed region), `any` the last ones of the trace whatever they are."""
 import csv, glob, sys
 d = sys.argv[1]
 back = int(sys.argv[2]) if len(sys.argv) > 2 else 2
