@@ -130,19 +130,7 @@ static int session_steps(mih_session_impl *s, int64_t nsteps, double *logl, int6
             if (v.res_begin(s->next_logl, s->best, s->steps, 0, &s->prm) == MIH_OK) rr.issued = rr.done = s->steps;
             else v.res_ok = false;
         }
-        if (v.res_active) {
-            ResRecord rec; bool aborted = false;
-            MIH_TRY(v.res_next(rr, &rec, &aborted));
-            if (aborted) MIH_TRY(v.res_end(&s->next_logl, &s->best, true));
-            else {
-                if (rec.status == RES_STOP_NAN || rec.status == RES_STOP_INF) {
-                    MIH_TRY(v.res_end(nullptr, nullptr));
-                    if (rec.status == RES_STOP_NAN) { set_error("Loglikelihood function is NaN, aborting..."); return MIH_NAN_LOGL; }
-                    set_error("Loglikelihood function is Inf, aborting..."); return MIH_INF_LOGL;
-                }
-                s->next_logl = rec.logl; nbt = rec.nbt; sc = rec.tol; stepped = true;
-            }
-        }
+        if (v.res_active) MIH_TRY(v.res_next(rr, &s->next_logl, &s->best, &nbt, &sc, &stepped));
         if (!stepped) {
             s->best = v.save_prev(s->next_logl, s->best);
             MIH_TRY(v.one_step(s->next_logl, s->prm.max_step, &nbt, &s->next_logl));

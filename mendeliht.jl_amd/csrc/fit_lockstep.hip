@@ -23,9 +23,6 @@ struct CvFit {
     int iter = 1, nbt = 0;
     double next_logl = -std::numeric_limits<double>::infinity(), best = -std::numeric_limits<double>::infinity();
     bool done = false;
-    // the lane's batched chain (k_lane_*): this fit wants its next step in the series the lane queues behind the pass / a series is in
-    // flight for it / its record has been read
-    bool wants_step = false, fresh_begin = false, in_batch = false, have_rec = false; ResRecord rec;
     // est_r in cv_iht: this fit is number chain_pos of chain `chain` (CvChains); when it ends it leaves its NegBin r in *chain_r
     int64_t chain = -1; size_t chain_pos = 0; double *chain_r = nullptr;
     // iht_run_many_models mode (no hold-out): where to put the finished model instead of a held-out deviance
@@ -184,10 +181,8 @@ struct CvQueue {
     std::vector<int> key;            // key[i]: what fit i shares its length with (the index of its k in the path); empty: plain order
     std::vector<int> seen;           // seen[key]: most iterations a finished fit of that key took (0: none finished)
     bool stop = false;               // an error somewhere: hand out nothing more
-    long unknown_bias = 0;
     void init(size_t n, std::vector<int> keys)
     {
-        if (const char *e = probe_env("MENDELIHT_CV_ORDER")) unknown_bias = !strcmp(e, "kdesc") ? 1 : !strcmp(e, "kasc") ? -1 : 0;
         total = n; ntaken = 0; taken.assign(n, 0); key = std::move(keys);
         int kmax = -1; for (int v : key) kmax = std::max(kmax, v);
         seen.assign((size_t)(kmax + 1), 0);
@@ -199,8 +194,7 @@ struct CvQueue {
         size_t best = total; long bestp = -1;
         for (size_t i = 0; i < total; ++i) {
             if (taken[i]) continue;
-            // (unknown lengths: in the caller's order, or -- measurement build, MENDELIHT_CV_ORDER=kdesc / kasc -- the larger / smaller model sizes first)
-            const long pr = key.empty() ? 0 : (seen[(size_t)key[i]] == 0 ? (1l << 30) + unknown_bias * (long)key[i] : (long)seen[(size_t)key[i]]);
+            const long pr = key.empty() ? 0 : (seen[(size_t)key[i]] == 0 ? (1l << 30) : (long)seen[(size_t)key[i]]);
             if (pr > bestp) { bestp = pr; best = i; }
             if (key.empty()) break;
         }
@@ -250,92 +244,12 @@ static int cv_run_rolling(const mih_mat *h, const mih_fit_params &pr, size_t tot
     hipEvent_t lane_ev = nullptr;         // "the lane's stream has got this far": the fits' streams wait for it behind the pass
     MIH_HIP(hipEventCreateWithFlags(&lane_ev, hipEventDisableTiming));
     struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } ev_guard{lane_ev};
-    // ---- the lane's batched chain (round 6): the records its kernels read, and the two halves of a round's step --------------------
-    // Which way a lane's resident fits step (tools/ab_cv_lanes.sh, tools/ab_cv_share.sh; configs[3], same box):
-    //   one chain per fit on the fit's own stream (lane_queue_step)   2.43-2.46 s for the 100 fits, 0.42-0.44 s for a rank's 13   <- the library
-    //   ONE batched chain per lane round (launch_series, k_lane_*)    2.58-2.63 s, 0.43-0.45 s     (measurement build: MENDELIHT_LANE_BATCHED=1)
-    //   host-driven steps (step_mode 1, rounds 1-5)                   2.42-2.49 s, 0.42-0.46 s
-    // The small kernels of a round can only run in the window between two fused passes (a pass's workgroups hold every CU), so what
-    // counts is their GPU time, not the host's waits: the batched chain needs 30 launches per round instead of ~250, but its two
-    // wide products (k_lane_xb, k_lane_xgk: 0.75 and 0.83 ms for 19 fits, 0.7 TB/s) and the attempt slots it queues for every fit
-    // whether it backtracks or not cost more than the launches saved.  Kept, bit for bit with the others, as the base for that work.
-    static const bool per_fit_chains = probe_env("MENDELIHT_LANE_BATCHED") == nullptr;
-    PinBuf<LaneFit> largs_h; DevBuf<LaneFit> largs_d;
-    { ArenaScope own_buffers(nullptr); MIH_TRY(largs_h.alloc((size_t)cap * 2, true)); MIH_TRY(largs_d.alloc((size_t)cap * 2)); }
-    struct DrainFirst { hipStream_t s; ~DrainFirst() { (void)hipStreamSynchronize(s); } } drain_first{s};      // (an error return: no kernel may still read the records above)
-    int largs_slot = 0;
-    std::vector<CvFit *> in_flight;                          // fits with a series of the batched chain queued and its record not read yet
-    // one series for `fits` on the lane's stream: (step_start) Z'r, df on the support, X_S df_S, the step size; then ONE attempt
-    auto launch_series = [&](std::vector<CvFit *> &fits, bool step_start) -> int {
-        const int F = (int)fits.size();
-        if (F == 0) return MIH_OK;
-        LaneFit *hp = largs_h.p + (size_t)largs_slot * cap; LaneFit *dp = largs_d.p + (size_t)largs_slot * cap;
-        largs_slot ^= 1;
-        const IhtVar &v0 = *fits[0]->v;
-        int64_t kc = 0; bool any_score = false;
-        for (int t = 0; t < F; ++t) {
-            IhtVar &v = *fits[(size_t)t]->v;
-            v.lane_seq = ++v.res_seq;
-            const bool new_score = step_start && !fits[(size_t)t]->fresh_begin;
-            v.lane_fill(hp[t], v.lane_seq, step_start, new_score);
-            any_score = any_score || new_score;
-            kc = std::max(kc, v.res_kcap);
-            fits[(size_t)t]->in_batch = true; fits[(size_t)t]->have_rec = false;
-        }
-        MIH_HIP(hipMemcpyAsync(dp, hp, sizeof(LaneFit) * (size_t)F, hipMemcpyHostToDevice, s));
-        const bool fix = v0.res_fix();
-        const unsigned wide = v0.res_wide_blocks(), nbk = (unsigned)v0.nb;
-        if (step_start) {
-            if (any_score) {
-                hipLaunchKernelGGL(k_lane_zt_r, dim3(kZtrBlocks, (unsigned)v0.q, (unsigned)F), dim3(256), 0, s, dp);
-                hipLaunchKernelGGL(k_lane_support, dim3((unsigned)nblk(kc), (unsigned)F), dim3(256), 0, s, dp);
-            }
-            if (!fix) hipLaunchKernelGGL(k_lane_xgk<false>, dim3(wide, (unsigned)F), dim3(kResWideRows), kResWideLds, s, dp);
-            else {
-                hipLaunchKernelGGL(k_lane_xgk<true>, dim3(wide, (unsigned)F), dim3(kResWideRows), kResWideLds, s, dp);
-                hipLaunchKernelGGL(k_lane_missing, dim3(1, (unsigned)F), dim3(1024), 0, s, dp, -1, 0);
-                hipLaunchKernelGGL(k_lane_stepsize, dim3(nbk, (unsigned)F), dim3(256), 0, s, dp);
-            }
-            hipLaunchKernelGGL(k_lane_eta, dim3(1, (unsigned)F), dim3(256), 0, s, dp);
-        }
-        // attempt slots: each serves whichever attempt a fit is due (its control block counts); a fit whose step has stood finds its
-        // gate closed in the slots behind.  The logistic fits of configs[3] backtrack about once per step, and a slot that turns out
-        // empty for every fit costs six launches that exit at once -- less than the round trip a series cut short would cost all
-        // of its fits: 1 + max_step slots, so a series always ends every step it began (attempt max_step stands: utilities.jl:484)
-        const int slots = 1 + std::max(0, pr.max_step);
-        for (int j = 0; j < slots; ++j) {
-            hipLaunchKernelGGL(k_lane_grad, dim3(kResGradBlocks, (unsigned)F), dim3(256), 0, s, dp);
-            hipLaunchKernelGGL(k_lane_hist2, dim3(kResHistBlocks, (unsigned)F), dim3(256), 0, s, dp);
-            hipLaunchKernelGGL(k_lane_collect, dim3(kResCollectBlocks, (unsigned)F), dim3(256), 0, s, dp);
-            hipLaunchKernelGGL(k_lane_select, dim3(1, (unsigned)F), dim3(1024), 0, s, dp);
-            if (!fix) hipLaunchKernelGGL(k_lane_xb<false>, dim3(wide, (unsigned)F), dim3(kResWideRows), kResWideLds, s, dp);
-            else {
-                hipLaunchKernelGGL(k_lane_xb<true>, dim3(wide, (unsigned)F), dim3(kResWideRows), kResWideLds, s, dp);
-                hipLaunchKernelGGL(k_lane_missing, dim3(1, (unsigned)F), dim3(1024), 0, s, dp, 0, 1);
-                hipLaunchKernelGGL(k_lane_mu, dim3(nbk, (unsigned)F), dim3(256), 0, s, dp);
-            }
-            hipLaunchKernelGGL(k_lane_decide, dim3(1, (unsigned)F), dim3(256), 0, s, dp, j + 1 < slots ? 1 : 0);
-        }
-        MIH_HIP(hipGetLastError());
-        return MIH_OK;
-    };
-    // the records of the series in flight; a fit whose step is still backtracking rides another series (its attempt counter says which
-    // attempt is due), until every fit's step has stood, stopped or been handed back
-    auto collect_series = [&]() -> int {
-        std::vector<CvFit *> again;
-        while (!in_flight.empty()) {
-            again.clear();
-            for (CvFit *f : in_flight) {
-                MIH_TRY(f->v->res_wait(f->v->lane_seq, &f->rec, s));
-                if (f->rec.status == RES_PENDING) { f->v->h->prof->count(MIH_CNT_RESIDENT_ATTEMPTS, 1); again.push_back(f); }
-                else { f->have_rec = true; f->in_batch = false; }
-            }
-            for (CvFit *f : again) f->fresh_begin = false;
-            MIH_TRY(launch_series(again, false));
-            in_flight = again;
-        }
-        return MIH_OK;
-    };
+    // A resident fit's step runs as a chain of its own on the fit's stream, queued behind the pass (lane_queue_step; configs[3]:
+    // 2.43-2.46 s for the 100 fits, host-driven steps 2.42-2.49 s).  The small kernels of a round can only run in the window between
+    // two fused passes (a pass's workgroups hold every CU), so what counts is their GPU time, not the host's waits.
+    // (declared behind the slots and the pool: on an error return the lane's stream, whose copies write the fits' df, drains before
+    // their IHTVariables go back to the matrix's reserve)
+    struct DrainFirst { hipStream_t s; ~DrainFirst() { (void)hipStreamSynchronize(s); } } drain_first{s};
     struct SlotOut { CvFit *f = nullptr; char fresh = 0; };
     std::vector<SlotOut> outs((size_t)cap);
     std::vector<std::function<int()>> tasks;
@@ -401,13 +315,8 @@ static int cv_run_rolling(const mih_mat *h, const mih_fit_params &pr, size_t tot
                 slot[t].reset(); continue;
             }
             // (round 6) a resident fit: the step's chain was queued behind the last pass (slot_post); its record is read here
-            bool stepped = false, dev_stop = false; double dev_tol = 0.0;
-            if (f.have_rec) {                                   // (the lane's batched chain: collect_series has read this fit's record)
-                bool again = false;
-                f.have_rec = false;
-                MIH_TRY(f.v->lane_take_record(f.rec, &f.next_logl, &f.best, &f.nbt, &dev_tol, &stepped, &again));
-            } else
-            MIH_TRY(f.v->lane_collect_step(&pr, &f.next_logl, &f.best, &f.nbt, &dev_tol, &stepped, &dev_stop));
+            bool stepped = false; double dev_tol = 0.0;
+            MIH_TRY(f.v->lane_collect_step(&pr, &f.next_logl, &f.best, &f.nbt, &dev_tol, &stepped));
             if (!stepped) {
                 f.best = f.v->save_prev(f.next_logl, f.best);
                 MIH_TRY(f.v->step_pre(f.next_logl, pr.max_step, &f.nbt, &f.next_logl));
@@ -441,21 +350,13 @@ static int cv_run_rolling(const mih_mat *h, const mih_fit_params &pr, size_t tot
             if (!f->v->res_active) MIH_TRY(f->v->step_post(f->next_logl));      // (debias! and the convergence test of this step ran before the pass: slot_pre)
             f->iter++;
         }
-        // the next step goes out now, behind the pass, without a wait (a fit that does not qualify steps host-driven in slot_pre):
-        // as one of the lane's batched series (launch_series, behind these tasks), or as a chain of its own on its stream
-        f->wants_step = false; f->fresh_begin = false;
+        // the next step goes out now, behind the pass, as a chain of its own on the fit's stream, without a wait (a fit that does not
+        // qualify steps host-driven in slot_pre)
         if (f->iter >= pr.max_iter || !f->v->res_ok) return MIH_OK;
-        if (per_fit_chains) return f->v->lane_queue_step(f->next_logl, f->best, f->iter - 1, &pr);
-        if (!f->v->res_active) {
-            if (f->v->res_begin(f->next_logl, f->best, f->iter - 1, 1, &pr) != MIH_OK) { f->v->res_ok = false; return MIH_OK; }
-            f->fresh_begin = true;
-        }
-        f->wants_step = true;
-        return MIH_OK;
+        return f->v->lane_queue_step(f->next_logl, f->best, f->iter - 1, &pr);
     };
     for (;;) {
         h->prof->count(MIH_CNT_ROUNDS, 1);
-        MIH_TRY(collect_series());                       // (every fit of this lane is quiescent again: what the hand-over below relies on)
         if (trace_rounds) {
             const double t = tnow();
             fprintf(stderr, "lane %d round %d: %.2f ms (before the pass %.2f ms, behind it %.2f ms of host time), %zu scores\n", lane_id, round_no++,
@@ -540,55 +441,8 @@ static int cv_run_rolling(const mih_mat *h, const mih_fit_params &pr, size_t tot
         tasks.clear();
         for (size_t t = 0; t < need.size(); ++t) { CvFit *f = need[t]; const char fr = fresh[t]; tasks.emplace_back([&slot_post, f, fr]() { return slot_post(f, fr); }); }
         MIH_TRY(sched.run(tasks));
-        {
-            std::vector<CvFit *> wants;
-            for (CvFit *f : need) if (f->wants_step) {
-                f->wants_step = false;
-                if (f->fresh_begin) MIH_TRY(fit_to_lane(*f, s));          // (res_begin's uploads went through the fit's own stream)
-                wants.push_back(f);
-            }
-            MIH_TRY(launch_series(wants, true));
-            for (CvFit *f : wants) { f->fresh_begin = false; in_flight.push_back(f); }
-        }
         t_post = tnow() - t_b;
     }
-    return MIH_OK;
-}
-
-// A lane's stream, on which its fused passes run.  (round 6) The passes leave a few CUs of the chip alone (a CU mask on the stream):
-// a fused pass's workgroups hold every CU they can get until the kernel's last wave of workgroups, so the small per-fit kernels of
-// BOTH lanes could only run in the window between two passes (228 ms of configs[3]'s 2.43 s); with `reserve` CUs kept
-// out of the passes' reach they run WHILE the other lane's pass is in flight.  The pass is bound by the matrix pipe under the
-// package power cap, not by the number of CUs: what it loses in CUs it gets back in clock (measured: tools/ab_cv_lanes.sh).
-static int lane_cu_reserve()
-{
-    static const int v = [] { const char *e = probe_env("MENDELIHT_LANE_CU_RESERVE"); return e ? atoi(e) : kLaneCuReserve; }();
-    return v;
-}
-static int lane_stream_create(const mih_mat *h, hipStream_t *out)
-{
-    const int reserve = lane_cu_reserve();
-    if (reserve > 0) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, h->device) == hipSuccess && pr.multiProcessorCount > 2 * reserve) {
-            const int cus = pr.multiProcessorCount, words = (cus + 31) / 32;
-            std::vector<uint32_t> mask((size_t)words, 0xffffffffu);
-            if (cus & 31) mask[(size_t)words - 1] = (1u << (cus & 31)) - 1u;
-            // Bit b of the mask is CU b / 8 of XCD b % 8 (tools/cu_mask_map.hip, profiles/r06_cu_mask_map.json), and a kernel's
-            // workgroups are dealt to the XCDs round-robin whatever CUs each has: the reserved CUs must come EVENLY from the XCDs, or
-            // the XCD that lost most is the straggler of every pass (the round's first attempt took every 32nd bit -- all of
-            // them CUs of XCD 7: 8 reserved CUs cost 25 %, 16 cost 66 %, and 32, a whole XCD, were not honoured at all).
-            const int xcds = (cus % 8 == 0 && cus >= 64) ? 8 : 1, per_xcd = cus / xcds, take = std::max(1, reserve / xcds);
-            for (int x = 0; x < xcds; ++x)
-                for (int t = 0; t < take; ++t) {
-                    const int b = (per_xcd - 1 - t * (per_xcd / take)) * xcds + x;
-                    mask[(size_t)(b >> 5)] &= ~(1u << (b & 31));
-                }
-            if (hipExtStreamCreateWithCUMask(out, (uint32_t)words, mask.data()) == hipSuccess) return MIH_OK;
-            (void)hipGetLastError();
-        } else (void)hipGetLastError();
-    }
-    MIH_HIP(hipStreamCreate(out));
     return MIH_OK;
 }
 
@@ -607,21 +461,17 @@ static int cv_run_lanes(const mih_mat *h, const mih_fit_params &pr, size_t total
     if (const char *e = probe_env("MENDELIHT_CV_LANES")) { int v = atoi(e); if (v >= 1 && v <= 4) lanes = (int)std::min<size_t>((size_t)v, total); }
     const int cap = (int)std::min<size_t>((size_t)std::max(1, width / lanes), (total + lanes - 1) / lanes);
     CvQueue queue;
-    queue.init(total, (chains || probe_env("MENDELIHT_CV_PLAIN_ORDER")) ? std::vector<int>() : queue_keys);
+    queue.init(total, chains ? std::vector<int>() : queue_keys);
     CvHandover handover;
     std::atomic<int> inflight[2];
     inflight[0].store(0); inflight[1].store(0);
     const bool merge_tail = lanes == 2 && !chains && !probe_env("MENDELIHT_CV_NO_MERGE");     // (a chain stays with its lane)
     std::vector<DevBuf<double>> yds((size_t)lanes), zds((size_t)lanes);
-    PassOrder pass_order;                                      // the lanes' fused passes in single file (common.h)
-    // (measured: neutral at configs[3] -- 2.74 s either way with per-fit chains, tools/ab_cv_lanes.sh -- so off unless asked for:
-    // MENDELIHT_CV_PASS_ORDER=1, measurement build)
-    const bool ordered = lanes > 1 && probe_env("MENDELIHT_CV_PASS_ORDER") != nullptr;
     auto lane = [&](int lane_id) -> int {
         PoolScope from_reserve(h->pool);                        // workspaces and IHTVariables out of the matrix's reserve (no hipMalloc)
         MIH_HIP(hipSetDevice(h->device));
         hipStream_t s = nullptr;
-        MIH_TRY(lane_stream_create(h, &s));
+        MIH_HIP(hipStreamCreate(&s));
         struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{s};
         XtvWork xw; DevBuf<double> R, DF;
         //  the workspace goes back to the matrix's reserve when this scope ends, on error returns too: nothing of this
@@ -629,11 +479,6 @@ static int cv_run_lanes(const mih_mat *h, const mih_fit_params &pr, size_t total
         struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } } drain{s};
         MIH_TRY(xtv_work_init(h, xw, cap, tune));
         xw.stream_tag = lane_id + 1;
-        hipEvent_t pass_done = nullptr;
-        if (ordered) MIH_HIP(hipEventCreateWithFlags(&pass_done, hipEventDisableTiming));
-        // (declared behind `drain`: destroyed first -- after this lane's last pass was queued, and an event another stream still waits on may be destroyed)
-        struct PassEv { hipEvent_t e; PassOrder *o; ~PassEv() { if (e) { std::lock_guard<std::mutex> g(o->mu); if (o->last == e) o->last = nullptr; (void)hipEventSynchronize(e); (void)hipEventDestroy(e); } } } pass_ev{pass_done, &pass_order};
-        if (ordered) { xw.order = &pass_order; xw.pass_done = pass_done; }
         h->prof->count(MIH_CNT_LANES, 1);
         MIH_TRY(R.alloc((size_t)cap * h->n));
         const int init_slots = std::min(init_keys, 8);          // shared initial scores (cv_run_rolling): 8 MB each at p = 1M
@@ -683,8 +528,6 @@ void mih::cv_assign(const int64_t *path, int64_t npath, int32_t nfolds, int32_t 
 {
     const int64_t total = (int64_t)nfolds * npath;
     rank_of.assign((size_t)total, 0);
-    const char *e = probe_env("MENDELIHT_CV_ASSIGN");               // measurement build: 0 = round 2's fold-major `index mod world`
-    if (e && atoi(e) == 0) { for (int64_t i = 0; i < total; ++i) rank_of[(size_t)i] = (int32_t)(i % world); return; }
     std::vector<int64_t> order((size_t)total);
     for (int64_t i = 0; i < total; ++i) order[(size_t)i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {

@@ -25,7 +25,6 @@
 namespace mih {
 
 constexpr int kMaxQ = 64;
-constexpr int kLaneCuReserve = 0;          // CUs a lock-step lane's fused passes leave to the per-fit kernels (lane_stream_create)
 struct QVec { double v[kMaxQ]; };
 
 // zc = Z c  (utilities.jl:113), optional clamp (utilities.jl:114-117)
@@ -1492,9 +1491,9 @@ struct IhtVar {
         res_sharded = comm != nullptr;
         if (comm && (!comm_is_native(comm, h->device) || has_weight || (int64_t)comm->world * K + q > kResMaxInBin || K + 64 > kResShardList)) return MIH_OK;
         // (round 6) a model beyond ~2000 effects ranks and orders its survivors in a scratch block of device memory (k_res_select_big)
-        // instead of LDS; beyond ~8000, in a column shard or in a lane's batched chain it takes the host-driven step
+        // instead of LDS; beyond ~8000 or in a column shard it takes the host-driven step
         res_big = K + 64 > kResMaxList;
-        if (res_big && (K + 64 > kResBigList || comm || (batched && probe_env("MENDELIHT_LANE_BATCHED")))) return MIH_OK;
+        if (res_big && (K + 64 > kResBigList || comm)) return MIH_OK;
         if (xv.slots <= 0 || xv.slots > (res_big ? 2 * kResBigList + 1024 : 160 * 32) || K < 1 || K > pg + q || h->p >= (1ll << 40)) return MIH_OK;
         res_kcap = std::min<int64_t>(kcap, (int64_t)xv.coefA.n);
         MIH_TRY(rctl.alloc(1)); MIH_TRY(ridx.alloc((size_t)res_kcap * 3)); MIH_TRY(rval.alloc((size_t)res_kcap * 3));
@@ -1791,18 +1790,16 @@ struct IhtVar {
     // res_begin): their projections take the direct gather, unless the forecast has failed three times in this run of steps.
     // first_slow: the attempt being re-queued because its forecast failed.
     int res_spec = 0, res_fast_fails = 0, res_known = 0, res_last[3] = {0, 0, 0};
-    static int res_spec_cap() { static const int c = probe_env("MENDELIHT_SPEC_CAP") ? atoi(probe_env("MENDELIHT_SPEC_CAP")) : 2; return c; }       // (measurement build: slots per series beyond the first)
+    static constexpr int kResSpecCap = 2;           // slots per series beyond the first
     int res_enqueue_attempts(uint64_t seq, int a0, int max_step, bool first_slow = false)
     {
         // A lane's fit (batched): ONE slot per series and no direct gather.  Its chain runs while the other lane's fused pass holds every
         // CU, where even a slot that turns out empty costs what its ~1500 workgroups cost to schedule (each needs a CU the pass has to
         // give up), and the fits of a cross-validation are short (5-17 steps): the threshold forecast failed in 13 % of their steps
         // (configs[3]: 150 redos in 1147 steps), as many as backtracked at all.  A step that backtracks costs its fit one more round trip.
-        static const bool lane_spec = probe_env("MENDELIHT_LANE_SPEC") != nullptr;          // (measurement build: the single fit's policy in the lanes)
-        const bool plain = batched && !lane_spec;
-        const int slots = plain ? 1 : 1 + std::max(0, std::min(max_step - std::min(a0, max_step), res_spec));      // (attempt max_step always stands: utilities.jl:484)
+        const int slots = batched ? 1 : 1 + std::max(0, std::min(max_step - std::min(a0, max_step), res_spec));      // (attempt max_step always stands: utilities.jl:484)
         for (int j = 0; j < slots; ++j) {
-            const bool fast = !plain && !res_big && res_known > 0 && res_fast_fails < 3 && !(first_slow && j == 0);
+            const bool fast = !batched && !res_big && res_known > 0 && res_fast_fails < 3 && !(first_slow && j == 0);
             if (fast) h->prof->count(MIH_CNT_RESIDENT_DIRECT, 1);
             MIH_TRY(res_enqueue_attempt(seq, 0, j + 1 < slots, fast));
         }
@@ -1831,10 +1828,8 @@ struct IhtVar {
     // between two kernels of the chain): the host polls the pinned ring -- briefly, then with short sleeps (it runs a step ahead of
     // the records it reads, and an X'r pass of tens of ms is in front of most of them), looking at the stream now and then so that a
     // failed launch does not leave it waiting.
-    // `on`: the stream the chain was queued on (a lane's batched series run on the LANE's stream, not on this fit's)
-    int res_wait(uint64_t seq, ResRecord *out, hipStream_t on = nullptr)
+    int res_wait(uint64_t seq, ResRecord *out)
     {
-        const hipStream_t sq = on ? on : s;
         volatile ResRecord *slot_ = rrec.p + (seq % kResRing);
         const auto t0 = std::chrono::steady_clock::now();
         auto next_query = t0 + std::chrono::milliseconds(50);
@@ -1847,7 +1842,7 @@ struct IhtVar {
             if (now - t0 > std::chrono::microseconds(200)) std::this_thread::sleep_for(std::chrono::microseconds(100));
             if (now > next_query) {
                 next_query = now + std::chrono::milliseconds(50);
-                const hipError_t e = hipStreamQuery(sq);
+                const hipError_t e = hipStreamQuery(s);
                 if (e == hipSuccess) {                     // everything queued has run: the record is there, or never will be
                     if (__atomic_load_n(&slot_->seq, __ATOMIC_ACQUIRE) == seq) break;
                     set_error("device-resident step %llu left no record", (unsigned long long)seq);
@@ -1859,12 +1854,38 @@ struct IhtVar {
         *out = *const_cast<ResRecord *>(slot_);
         return MIH_OK;
     }
-    // One accepted step of the resident chain (the chain itself runs up to two steps ahead of this call, never past rr.limit
-    // steps in all).  *aborted: the device met a case it leaves to the host-driven step (ties for _choose!, lists beyond its
-    // buffers): the iterate is back on the host as it was when that step began, nothing of it has been applied.
-    int res_next(ResRun &rr, ResRecord *rec, bool *aborted)
+    // What the record of a step means for this fit: the cases res_next and lane_collect_step share (PENDING and REDO_SLOW stay with
+    // them: what each queues again differs).  The step stood (ACCEPT, or STOP_CONVERGED: the device applied the stopping rule,
+    // fit.jl:197, and it held): its backtracks are the forecast of the slots the next steps get, *stepped = true.  ABORT: the device
+    // met a case it leaves to the host-driven step (ties for _choose!, lists beyond its buffers) -- the iterate is back on the host as
+    // it was when that step began, nothing of it has been applied, *stepped = false.  NaN / Inf: the iterate comes home, the fit fails.
+    int res_take(const ResRecord &rec, double *next_logl, double *best, int *nbt, double *tol, bool *stepped)
     {
-        *aborted = false;
+        *stepped = false;
+        switch (rec.status) {
+        case RES_ACCEPT: case RES_STOP_CONVERGED:
+            res_known = std::max(res_known, rec.nbt + 1);
+            res_last[2] = res_last[1]; res_last[1] = res_last[0]; res_last[0] = rec.nbt;
+            res_spec = std::min(kResSpecCap, std::max(res_last[0], std::max(res_last[1], res_last[2])));
+            h->prof->count(MIH_CNT_RESIDENT_STEPS, 1);
+            if (rec.status == RES_STOP_CONVERGED) ++res_epoch;
+            *next_logl = rec.logl; *nbt = rec.nbt; *tol = rec.tol; *stepped = true;
+            return MIH_OK;
+        case RES_STOP_NAN: case RES_STOP_INF:
+            ++res_epoch;
+            MIH_TRY(res_end(nullptr, nullptr));
+            if (rec.status == RES_STOP_NAN) { set_error("Loglikelihood function is NaN, aborting..."); return MIH_NAN_LOGL; }
+            set_error("Loglikelihood function is Inf, aborting..."); return MIH_INF_LOGL;
+        case RES_ABORT:
+            h->prof->count(MIH_CNT_RESIDENT_HANDBACKS, 1);
+            return res_end(next_logl, best, true);
+        default: set_error("device-resident step: unknown record status %d", rec.status); return MIH_HIP_ERROR;
+        }
+    }
+    // One step of the resident chain (the chain itself runs up to two steps ahead of this call, never past rr.limit steps in all);
+    // the record means what res_take says.
+    int res_next(ResRun &rr, double *next_logl, double *best, int *nbt, double *tol, bool *stepped)
+    {
         for (;;) {
             while (rr.issued < rr.limit && res_out.size() < 2) {
                 const uint64_t seq = ++res_seq;
@@ -1874,39 +1895,33 @@ struct IhtVar {
             if (res_out.empty()) { set_error("no device-resident step in flight"); return MIH_BAD_ARG; }
             const uint64_t seq = res_out.front();
             res_out.erase(res_out.begin());
-            MIH_TRY(res_wait(seq, rec));
-            switch (rec->status) {
-            case RES_ACCEPT:
-                ++rr.done; res_known = std::max(res_known, rec->nbt + 1);
-                res_last[2] = res_last[1]; res_last[1] = res_last[0]; res_last[0] = rec->nbt;
-                res_spec = std::min(res_spec_cap(), std::max(res_last[0], std::max(res_last[1], res_last[2])));
-                h->prof->count(MIH_CNT_RESIDENT_STEPS, 1);
-                return MIH_OK;
+            ResRecord rec;
+            MIH_TRY(res_wait(seq, &rec));
+            switch (rec.status) {
+            case RES_ACCEPT: ++rr.done; break;
             case RES_PENDING:                // the series ended with the step still backtracking: the series queued behind goes on with it
                 res_dead_pass_at((int)res_out.size());       // (the step-end kernels in between, the X'r pass among them, did nothing)
                 --rr.issued;
                 h->prof->count(MIH_CNT_RESIDENT_ATTEMPTS, 1);
-                break;
+                continue;
             case RES_REDO_SLOW: {            // the direct gather's forecast failed: the same attempt again, with the histograms
                 res_dead_passes(1 + (int)res_out.size());
                 ++res_epoch; res_out.clear(); rr.issued = rr.done;
                 ++res_fast_fails;
                 h->prof->count(MIH_CNT_RESIDENT_REDOS, 1);
                 const uint64_t s2 = ++res_seq;
-                MIH_TRY(res_enqueue_attempts(s2, rec->nbt, rr.max_step, true)); MIH_TRY(res_enqueue_back());
+                MIH_TRY(res_enqueue_attempts(s2, rec.nbt, rr.max_step, true)); MIH_TRY(res_enqueue_back());
                 res_out.push_back(s2); ++rr.issued;
+                continue;
+            }
+            case RES_STOP_CONVERGED: case RES_STOP_NAN: case RES_STOP_INF: case RES_ABORT:     // nothing queued behind it is to run
+                res_dead_passes(1 + (int)res_out.size());
+                res_out.clear();
+                if (rec.status != RES_ABORT) ++rr.done;
+                rr.issued = rr.done;
                 break;
             }
-            case RES_STOP_CONVERGED: res_dead_passes(1 + (int)res_out.size()); ++res_epoch; res_out.clear(); ++rr.done; rr.issued = rr.done; h->prof->count(MIH_CNT_RESIDENT_STEPS, 1); return MIH_OK;
-            case RES_STOP_NAN: case RES_STOP_INF: res_dead_passes(1 + (int)res_out.size()); ++res_epoch; res_out.clear(); ++rr.done; rr.issued = rr.done; return MIH_OK;
-            case RES_ABORT:
-                res_dead_passes(1 + (int)res_out.size());
-                res_out.clear(); rr.issued = rr.done;      // (res_end moves the epoch on)
-                h->prof->count(MIH_CNT_RESIDENT_HANDBACKS, 1);
-                *aborted = true;
-                return MIH_OK;
-            default: set_error("device-resident step: unknown record status %d", rec->status); return MIH_HIP_ERROR;
-            }
+            return res_take(rec, next_logl, best, nbt, tol, stepped);
         }
     }
 
@@ -1934,10 +1949,10 @@ struct IhtVar {
         return MIH_OK;
     }
     // *stepped = false: no chain was queued, or the device handed the step back (the iterate is home again): the host-driven step_pre
-    // follows.  *stop: the device applied the stopping rule (fit.jl:197) and it held.
-    int lane_collect_step(const mih_fit_params *prm, double *next_logl, double *best, int *nbt, double *tol, bool *stepped, bool *stop)
+    // follows.  Otherwise the record means what res_take says.
+    int lane_collect_step(const mih_fit_params *prm, double *next_logl, double *best, int *nbt, double *tol, bool *stepped)
     {
-        *stepped = false; *stop = false;
+        *stepped = false;
         if (!lane_queued) return MIH_OK;
         lane_queued = false;
         uint64_t seq = lane_seq;
@@ -1945,73 +1960,19 @@ struct IhtVar {
             ResRecord rec;
             MIH_TRY(res_wait(seq, &rec));
             switch (rec.status) {
-            case RES_ACCEPT: case RES_STOP_CONVERGED:
-                res_known = std::max(res_known, rec.nbt + 1);
-                res_last[2] = res_last[1]; res_last[1] = res_last[0]; res_last[0] = rec.nbt;
-                res_spec = std::min(res_spec_cap(), std::max(res_last[0], std::max(res_last[1], res_last[2])));
-                h->prof->count(MIH_CNT_RESIDENT_STEPS, 1);
-                if (rec.status == RES_STOP_CONVERGED) { ++res_epoch; *stop = true; }
-                *next_logl = rec.logl; *nbt = rec.nbt; *tol = rec.tol; *stepped = true;
-                return MIH_OK;
             case RES_PENDING:                // the series ended with the step still backtracking: another series of slots goes on with it
                 h->prof->count(MIH_CNT_RESIDENT_ATTEMPTS, 1);
                 seq = ++res_seq;
                 MIH_TRY(res_enqueue_attempts(seq, rec.nbt, prm->max_step));
-                break;
+                continue;
             case RES_REDO_SLOW:              // the direct gather's forecast failed: the same attempt again, with the histograms
                 ++res_epoch; ++res_fast_fails;
                 h->prof->count(MIH_CNT_RESIDENT_REDOS, 1);
                 seq = ++res_seq;
                 MIH_TRY(res_enqueue_attempts(seq, rec.nbt, prm->max_step, true));
-                break;
-            case RES_STOP_NAN: case RES_STOP_INF:
-                ++res_epoch;
-                MIH_TRY(res_end(nullptr, nullptr));
-                if (rec.status == RES_STOP_NAN) { set_error("Loglikelihood function is NaN, aborting..."); return MIH_NAN_LOGL; }
-                set_error("Loglikelihood function is Inf, aborting..."); return MIH_INF_LOGL;
-            case RES_ABORT:
-                h->prof->count(MIH_CNT_RESIDENT_HANDBACKS, 1);
-                return res_end(next_logl, best, true);
-            default: set_error("device-resident step: unknown record status %d", rec.status); return MIH_HIP_ERROR;
+                continue;
             }
-        }
-    }
-
-    // ... and BATCHED over the lane's fits (k_lane_*, resident.inc): this fit's record of the array the lane's kernels read.
-    // step_start: the step begins here (X_S df_S, the step size); new_score: Z'r and df on the support are taken from the score that
-    // has just arrived (not for a fit res_begin has just set up: it brought them along)
-    void lane_fill(LaneFit &a, uint64_t seq, bool step_start, bool new_score) const
-    {
-        static const int force_abort_es = probe_env("MENDELIHT_RES_FORCE_ABORT_ES") ? atoi(probe_env("MENDELIHT_RES_FORCE_ABORT_ES")) : -1;
-        a.P = res_ptrs(); a.M = res_mat(); a.epoch = res_epoch; a.front = step_start ? 1 : 0; a.score = new_score ? 1 : 0;
-        a.q = q; a.dist = dist; a.link = link; a.zkeepn = (int)zkeepn; a.lean = res_lean() ? 1 : 0; a.force_abort_es = force_abort_es;
-        a.nb_r = nb_r; a.zkeep = res_zkeep_mask(); a.K = (uint64_t)(k + zkeepn); a.seq = seq;
-        a.max_nonzero = ((J == 0) ? 1 : J) * (k + zkeepn); a.p = p;
-        a.z = z.p; a.y = y.p; a.w = w.p; a.weight = has_weight ? weight.p : nullptr;
-        a.xb = xb.p; a.zc = zc.p; a.mu = mu.p; a.r = r.p; a.xgk = xgk.p; a.red = red.p; a.df = df.p; a.full = full.p;
-        a.ztr = ztr.p; a.df2 = rctl.p->df2; a.ztr_done = ztr_done.p; a.nb = nb; a.pad = 0;
-    }
-    // what a record of the batched chain means for this fit (the cases of lane_collect_step).  *again: the step is still backtracking,
-    // the lane queues another series for it
-    int lane_take_record(const ResRecord &rec, double *next_logl, double *best, int *nbt, double *tol, bool *stepped, bool *again)
-    {
-        *stepped = false; *again = false;
-        switch (rec.status) {
-        case RES_ACCEPT: case RES_STOP_CONVERGED:
-            h->prof->count(MIH_CNT_RESIDENT_STEPS, 1);
-            if (rec.status == RES_STOP_CONVERGED) ++res_epoch;
-            *next_logl = rec.logl; *nbt = rec.nbt; *tol = rec.tol; *stepped = true;
-            return MIH_OK;
-        case RES_PENDING: h->prof->count(MIH_CNT_RESIDENT_ATTEMPTS, 1); *again = true; return MIH_OK;
-        case RES_STOP_NAN: case RES_STOP_INF:
-            ++res_epoch;
-            MIH_TRY(res_end(nullptr, nullptr));
-            if (rec.status == RES_STOP_NAN) { set_error("Loglikelihood function is NaN, aborting..."); return MIH_NAN_LOGL; }
-            set_error("Loglikelihood function is Inf, aborting..."); return MIH_INF_LOGL;
-        case RES_ABORT:
-            h->prof->count(MIH_CNT_RESIDENT_HANDBACKS, 1);
-            return res_end(next_logl, best, true);
-        default: set_error("device-resident step: unknown record status %d", rec.status); return MIH_HIP_ERROR;
+            return res_take(rec, next_logl, best, nbt, tol, stepped);
         }
     }
 
@@ -2037,19 +1998,7 @@ struct IhtVar {
                 if (res_begin(next_logl, best, iter - 1, 1, prm) == MIH_OK) rr.issued = rr.done = iter - 1;
                 else res_ok = false;
             }
-            if (res_active) {
-                ResRecord rec; bool aborted = false;
-                MIH_TRY(res_next(rr, &rec, &aborted));
-                if (aborted) MIH_TRY(res_end(&next_logl, &best, true));
-                else {
-                    if (rec.status == RES_STOP_NAN || rec.status == RES_STOP_INF) {
-                        MIH_TRY(res_end(nullptr, nullptr));
-                        if (rec.status == RES_STOP_NAN) { set_error("Loglikelihood function is NaN, aborting..."); return MIH_NAN_LOGL; }
-                        set_error("Loglikelihood function is Inf, aborting..."); return MIH_INF_LOGL;
-                    }
-                    next_logl = rec.logl; nbt = rec.nbt; sc = rec.tol; stepped = true;
-                }
-            }
+            if (res_active) MIH_TRY(res_next(rr, &next_logl, &best, &nbt, &sc, &stepped));
             if (!stepped) {
                 // the host-driven step.  debias! (fit.jl:188) and the convergence test (fit.jl:197) read b, b0, c, c0 only, so they run
                 // in front of the X'r pass that ends the step; a fit that converges here skips that pass (the reference computes the

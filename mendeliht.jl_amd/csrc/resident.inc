@@ -1508,114 +1508,3 @@ k_res_peel(ResPtrs P, int epoch, const double *__restrict__ r, int64_t n, const 
     const int64_t nb64 = (n + 255) / 256;
     (void)peel_decide(r, n, spart, (int)(nb64 < kStatBlocksRes ? nb64 : kStatBlocksRes), pl);
 }
-
-// ---- a lock-step lane's fits, BATCHED (round 6) ---------------------------------------------------------------------------------
-// The fits of a lane advance together: ONE fused X'R pass scores all of them, and between two passes every fit takes one
-// iht_one_step! up to its working residual.  Queued per fit that is 10 - 12 launches each (200 - 500 per round for 19 fits), and the
-// chains can only run in the windows between two passes -- a pass's workgroups hold every CU, nothing of another stream gets in
-// (tools/cv_window_trace.sh: 8 - 20 ms of small kernels per window, a tenth of a round).  Here the same kernel bodies run ONCE per
-// round for all fits of the lane: blockIdx.y (blockIdx.z for Z'r) is the fit, its arguments come from an array of LaneFit records.
-// Every fit keeps its own control block, gate word, attempt counter and record ring, so fits backtrack, stop and hand steps back
-// independently: a series of attempt kernels serves whichever attempt each fit is due, fits that have finished their step find
-// their gate closed.  The arithmetic of a fit is that of its own chain: same bits as step_mode 1 and as a fit on its own.
-struct LaneFit {
-    ResPtrs P; ResMat M;
-    int32_t epoch;
-    int32_t front;                        // the step starts in this series (X_S df_S, the step size); 0: a series that goes on with a backtracking step
-    int32_t score;                        // ... and Z'r and df on the support are taken from the score that has just arrived
-    int32_t q, dist, link, zkeepn, lean, force_abort_es, pad0;
-    double nb_r;
-    uint64_t zkeep, K, seq;
-    int64_t max_nonzero, p;
-    const double *z, *y, *w, *weight;
-    double *xb, *zc, *mu, *r, *xgk, *red, *df, *full, *ztr, *df2;
-    unsigned *ztr_done;
-    int32_t nb, pad;
-};
-static __global__ void __launch_bounds__(256)
-k_lane_zt_r(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.z];
-    if (!a.score || (int)blockIdx.y >= a.q) return;
-    b_zt_r((int)blockIdx.y, (int)blockIdx.x, a.z, a.r, a.M.n, a.ztr, a.ztr_done, a.df2);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_support(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    if (!a.score) return;
-    b_res_support(a.P, a.epoch, a.M, a.df);
-}
-template <bool SPLIT>
-__global__ void __launch_bounds__(1024, 8)
-k_lane_xgk(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    if (!a.front) return;
-    b_res_xgk<SPLIT>(a.P, a.epoch, a.M, a.z, a.xb, a.zc, a.mu, a.w, a.q, a.dist, a.link, a.nb_r, a.xgk, a.red);
-}
-static __global__ void __launch_bounds__(1024)
-k_lane_missing(const LaneFit *__restrict__ L, int attempt, int which)
-{
-    const LaneFit &a = L[blockIdx.y];
-    if (attempt < 0 && !a.front) return;
-    b_res_missing(a.P, a.epoch, attempt, which, a.M, which ? a.xb : a.xgk);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_stepsize(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    if (!a.front) return;
-    b_res_stepsize(a.P, a.epoch, a.xgk, a.z, a.xb, a.zc, a.mu, a.w, a.M.n, a.q, a.dist, a.link, a.nb_r, a.red);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_eta(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    if (!a.front) return;
-    b_res_eta(a.P, a.epoch, a.red, a.nb, a.q, nullptr);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_grad(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_grad<false>(a.P, a.epoch, 0, a.df, a.weight, a.p, a.q, a.zkeep, a.p + a.q, a.full);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_hist2(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_hist2(a.P, a.epoch, 0, a.full, a.p + a.q, a.K);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_collect(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_collect(a.P, a.epoch, 0, a.full, a.p + a.q);
-}
-static __global__ void __launch_bounds__(1024)
-k_lane_select(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_select(a.P, a.epoch, 0, 0, a.K, a.seq, a.M, a.weight, a.p, a.q, a.zkeep, a.zkeepn, a.max_nonzero, a.force_abort_es);
-}
-template <bool SPLIT>
-__global__ void __launch_bounds__(1024, 8)
-k_lane_xb(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_xb<SPLIT>(a.P, a.epoch, 0, a.M, a.z, a.y, a.w, a.q, a.dist, a.link, a.nb_r, a.xb, a.zc, a.mu, a.red, a.r, a.lean);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_mu(const LaneFit *__restrict__ L)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_mu(a.P, a.epoch, 0, a.xb, a.z, a.y, a.w, a.M.n, a.q, a.dist, a.link, a.nb_r, a.xb, a.zc, a.mu, a.red, a.r);
-}
-static __global__ void __launch_bounds__(256)
-k_lane_decide(const LaneFit *__restrict__ L, int next_attempt_queued)
-{
-    const LaneFit &a = L[blockIdx.y];
-    b_res_decide(a.P, a.epoch, 0, next_attempt_queued, a.seq, a.red, a.nb, a.M.n, a.dist);
-}
-

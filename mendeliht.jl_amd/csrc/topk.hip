@@ -452,8 +452,7 @@ static int topk_two_pass(double *x_dev, int64_t len, int64_t k, TopkWork &w, hip
     const int64_t first = std::min<int64_t>(w.expect, w.cap);
     // (round 6) the exact finish on the device: the survivors come home ranked and ordered (k_topk_finish); the host's own finish
     // below stays for more candidates than that kernel ranks
-    static const bool host_finish = probe_env("MENDELIHT_TOPK_HOST_FINISH") != nullptr;        // (measurement build: rounds 1-5's finish)
-    if (!host_finish && w.fin.p) {
+    if (w.fin.p) {
         hipLaunchKernelGGL(k_topk_finish, dim3(1), dim3(1024), 0, s, w.sel.p, (uint32_t)w.cap, (uint64_t)k, w.state.p, w.fin.p);
         if (zero_in_place) hipLaunchKernelGGL(k_zero_below_dev, dim3(grid), dim3(256), 0, s, x_dev, len, w.fin.p);
         const int64_t fcap = std::min<int64_t>(first, kFinishCap);

@@ -20,10 +20,11 @@ def test_library_exports_every_declared_symbol(mih):
         assert getattr(L, s) is not None
 
 
-def test_probe_entry_points_live_in_the_measurement_build_only(mih):
+def test_probe_entry_points_and_live_switches_in_the_measurement_build_only(mih):
     """Kernel-shape knobs and timing probes are not part of the product: libmendeliht_hip.so exports exactly the header's
     functions, the measurement build (-DMIH_PROBES) those plus include/mendeliht_hip_probes.h; the product has no mutable
-    process-wide selectors (mih_set_*) and reads none of the MENDELIHT_* A/B switches."""
+    process-wide selectors (mih_set_*) and reads none of the MENDELIHT_* A/B switches.  The switches of measured dead ends that
+    were retired with their code are in neither build."""
     import ctypes as C
     import subprocess
     from mendeliht_amd import api
@@ -41,10 +42,16 @@ def test_probe_entry_points_live_in_the_measurement_build_only(mih):
     blob = open(mih.library_path(), "rb").read()
     for switch in (b"MENDELIHT_XTV_MAX_OPS", b"MENDELIHT_XTV_SLICES", b"MENDELIHT_XTV_NO_HALF", b"MENDELIHT_CV_LANES", b"MENDELIHT_CV_NO_MERGE",
                    b"MENDELIHT_CV_NO_INIT_SHARE", b"MENDELIHT_CV_TRACE", b"MENDELIHT_NO_SPIN", b"MENDELIHT_NO_ARENA", b"MENDELIHT_TOPK_RADIX8",
-                   b"MENDELIHT_XV_MULTI", b"MENDELIHT_CV_ASSIGN", b"MENDELIHT_CV_NO_COOP", b"MENDELIHT_COOP_SPIN_US", b"MENDELIHT_INGEST_TRACE",
+                   b"MENDELIHT_XV_MULTI", b"MENDELIHT_CV_NO_COOP", b"MENDELIHT_COOP_SPIN_US", b"MENDELIHT_INGEST_TRACE",
                    b"MENDELIHT_NO_RESERVE", b"MENDELIHT_INGEST_THREADS"):
         assert switch not in blob, switch
         assert switch in open(mih.probes_library_path(), "rb").read(), switch
+    # the A/B paths measured and retired stay out of both builds
+    for switch in (b"MENDELIHT_LANE_BATCHED", b"MENDELIHT_LANE_CU_RESERVE", b"MENDELIHT_CV_PASS_ORDER", b"MENDELIHT_WORKER_PRIORITY",
+                   b"MENDELIHT_CV_ORDER", b"MENDELIHT_CV_PLAIN_ORDER", b"MENDELIHT_LANE_SPEC", b"MENDELIHT_SPEC_CAP", b"MENDELIHT_CV_ASSIGN",
+                   b"MENDELIHT_TOPK_HOST_FINISH", b"MENDELIHT_LANE_PER_FIT"):
+        assert switch not in blob, switch
+        assert switch not in open(mih.probes_library_path(), "rb").read(), switch
     #  the product reads ONE environment variable: where to find librccl.  The reserve of device memory is an
     # argument now (mih_mat_reserve), the number of upload workers is fixed by the library
     assert set(re.findall(rb"MENDELIHT_[A-Z0-9_]+", blob)) == {b"MENDELIHT_RCCL_LIB"}

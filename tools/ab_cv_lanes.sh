@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/ab_cv_lanes.sh -- cv_iht at configs[3] size on the MEASUREMENT build, separate processes on one box: the lanes' fits resident
-# (step_mode 0) or host-driven (1), with / without the single-file order of the lanes' passes and the worker streams' priority.
+# (step_mode 0) or host-driven (1), and the hash of their losses (the two must agree bit for bit).
 cd $GRAFT_REPO_ROOT
 run() {  # name, env...
   name=$1; shift
@@ -26,11 +26,6 @@ print(json.dumps({"variant": sys.argv[1], "seconds": ts[1:], "hash": hashlib.sha
 PY
 }
 for rep in 1 2; do
-run "host-driven, no CUs reserved" MIH_MODE=1 MENDELIHT_LANE_CU_RESERVE=0
-run "host-driven, 8 CUs reserved" MIH_MODE=1 MENDELIHT_LANE_CU_RESERVE=8
-run "resident per fit, no CUs reserved" MIH_MODE=0 MENDELIHT_LANE_CU_RESERVE=0
-run "resident per fit, 8 CUs reserved" MIH_MODE=0 MENDELIHT_LANE_CU_RESERVE=8
-run "resident per fit, 16 CUs reserved" MIH_MODE=0 MENDELIHT_LANE_CU_RESERVE=16
-run "resident per fit, 32 CUs reserved" MIH_MODE=0 MENDELIHT_LANE_CU_RESERVE=32
-run "resident batched, 16 CUs reserved" MIH_MODE=0 MENDELIHT_LANE_CU_RESERVE=16 MENDELIHT_LANE_BATCHED=1
+run "host-driven" MIH_MODE=1
+run "resident per fit" MIH_MODE=0
 done
