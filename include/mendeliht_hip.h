@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.4: round 4 of this header (cv_threads, mih_cv_allgather, column-sharded lock-step drivers) */
+int mih_version(int *major, int *minor);     /* 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -85,6 +85,20 @@ int mih_dense_create(const double *x, int64_t n, int64_t p, int device, mih_mat 
  * reference's all-Float32 run. */
 int mih_dense_create_f32(const float *x, int64_t n, int64_t p, int device, mih_mat **out);
 int mih_dense_create_synthetic(int64_t n, int64_t p, uint64_t seed, int device, mih_mat **out);
+/* Genotype dosages (VCF DS / GT, BGEN) on the grid d = num / denom in [0, 2], stored as 16-bit numerators: 4x less HBM
+ * than the reference's dense Matrix{Float64} of the same values.  num is n x p column-major with column stride col_stride
+ * (>= n); 1 <= denom <= 32767; 0xFFFF marks a missing entry, any other num > 2 denom is MIH_BAD_ARG.  The handle is a dense
+ * matrix to every fit and holds the STANDARDIZED genotypes of standardize_genotypes! (src/wrapper.jl:406-423), as
+ * SnpLinAlg(center, scale, impute) does: mu_j = mean of the non-missing d, sigma_j = sqrt(mu_j (1 - mu_j / 2)),
+ * x_ij = (d_ij - mu_j) / sigma_j (d_ij - mu_j where sigma_j = 0), 0 where missing (imputed by the mean); an all-missing
+ * column is all zeros.  (The reference's own function throws on a missing entry: wrapper.jl:411 reads an undefined `t`.) */
+int mih_dosage_create(const uint16_t *num, int64_t n, int64_t p, int64_t col_stride, int32_t denom, int device, mih_mat **out);
+/* A seeded synthetic dosage matrix generated on the device (no host upload): hard calls Binomial(2, rho_j),
+ * rho_j ~ U(0, 0.5), moved by up to +-0.1 on the grid of denom and clamped to [0, 2]; each entry missing with
+ * probability missing_rate. */
+int mih_dosage_create_synthetic(int64_t n, int64_t p, uint64_t seed, int32_t denom, double missing_rate, int device, mih_mat **out);
+/* Numerators of columns [col0, col0 + ncols) of a dosage handle into out (n x ncols column-major, 0xFFFF = missing). */
+int mih_dosage_export(const mih_mat *h, int64_t col0, int64_t ncols, uint16_t *out);
 /* Releases the matrix.  A mih_session must not be stepped after its matrix is gone, but it may be destroyed later: the
  * reserve of device memory a large matrix keeps for its fits lives until its last user. */
 int mih_mat_destroy(mih_mat *h);
@@ -94,7 +108,7 @@ int mih_mat_destroy(mih_mat *h);
  * Not to be called while a fit is running on the matrix.  MIH_OOM if the device has less than four times the size free. */
 int mih_mat_reserve(mih_mat *h, int64_t bytes);
 int mih_mat_dims(const mih_mat *h, int64_t *n, int64_t *p);
-/* `x.μ`, `x.σinv` of the SnpLinAlg */
+/* `x.μ`, `x.σinv` of the SnpLinAlg, or mu_j (dosage units) and 1/sigma_j (1 where sigma_j = 0) of a dosage handle */
 int mih_snp_mu_sigma(const mih_mat *h, double *mu, double *sinv);
 /* Re-encode the device matrix as PLINK .bed columns (ceil(n/4) bytes each): lets a
  * synthetic matrix be handed to any other PLINK consumer. */

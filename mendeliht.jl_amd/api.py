@@ -146,6 +146,9 @@ def lib():
         "mih_dense_create": [vp, i64, i64, C.c_int, C.POINTER(vp)],
         "mih_dense_create_synthetic": [i64, i64, C.c_uint64, C.c_int, C.POINTER(vp)],
         "mih_dense_create_f32": [vp, i64, i64, C.c_int, C.POINTER(vp)],
+        "mih_dosage_create": [vp, i64, i64, i64, i32, C.c_int, C.POINTER(vp)],
+        "mih_dosage_create_synthetic": [i64, i64, C.c_uint64, i32, dbl, C.c_int, C.POINTER(vp)],
+        "mih_dosage_export": [vp, i64, i64, vp],
         "mih_mat_destroy": [vp],
         "mih_mat_dims": [vp, C.POINTER(i64), C.POINTER(i64)],
         "mih_mat_reserve": [vp, i64],
@@ -201,7 +204,8 @@ def exported_symbols():
     """Every symbol include/mendeliht_hip.h declares (checked by the CPU test-suite)."""
     return ["mih_device_count", "mih_last_error", "mih_version", "mih_snp_create", "mih_snp_create_synthetic",
             "mih_snp_create_synthetic_shard",
-            "mih_dense_create", "mih_dense_create_synthetic", "mih_dense_create_f32", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
+            "mih_dense_create", "mih_dense_create_synthetic", "mih_dense_create_f32",
+            "mih_dosage_create", "mih_dosage_create_synthetic", "mih_dosage_export", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
@@ -531,6 +535,65 @@ class DenseMatrix(_Mat):
         h = C.c_void_p(None)
         _check(lib().mih_dense_create_synthetic(n, p, seed, device, C.byref(h)))
         return cls(None, device=device, _handle=h)
+
+
+class DosageMatrix(_Mat):
+    """Genotype dosages d = num / denom in [0, 2] (VCF DS / GT, BGEN), resident in HBM as 16-bit numerators: 4x less memory
+    and X'r traffic than the reference's Matrix{Float64} of the same values.  `num` is n x p, 0xFFFF marks a missing entry,
+    1 <= denom <= 32767.  The matrix every fit sees is the STANDARDIZED one of standardize_genotypes! (src/wrapper.jl:406-423)
+    -- mu_j the mean of the non-missing d, sigma_j = sqrt(mu_j (1 - mu_j / 2)), x_ij = (d_ij - mu_j) / sigma_j (d_ij - mu_j
+    where sigma_j = 0), missing entries imputed by the mean (0), all-missing columns zero -- which is SnpLinAlg(center=true,
+    scale=true, impute=true) on these values.  (The reference's own function throws on any missing entry: wrapper.jl:411 reads
+    an undefined `t`.)"""
+
+    def __init__(self, num, denom, device=0, _handle=None):
+        super().__init__()
+        self.device = device
+        self.denom = int(denom)
+        self.dtype = np.float64
+        if _handle is not None:
+            self._h = _handle
+            self._dims()
+            return
+        num = np.asarray(num)
+        if num.ndim != 2:
+            raise DimensionMismatch("num must be a matrix")
+        if num.dtype != np.uint16:
+            raise ArgumentError(f"num must be uint16 (0xFFFF = missing), got {num.dtype}")
+        num = np.asfortranarray(num)
+        h = C.c_void_p(None)
+        _check(lib().mih_dosage_create(_p(num), num.shape[0], num.shape[1], num.shape[0], self.denom, device, C.byref(h)))
+        self._h = h
+        self._dims()
+
+    @classmethod
+    def from_dosages(cls, d, device=0):
+        """Dosages as floats (NaN = missing); the grid num / denom is detected (hard calls, up to 4 decimals, B <= 15 bit
+        probabilities) and reduced by the gcd.  ArgumentError if the values sit on no grid with denom <= 32767."""
+        from .genotypes import dosage_grid
+        num, denom = dosage_grid(np.asarray(d, dtype=np.float64))
+        return cls(num, denom, device=device)
+
+    @classmethod
+    def synthetic(cls, n, p, seed=2024, denom=255, missing_rate=0.0, device=0):
+        """A seeded n x p dosage matrix generated on the device: hard calls Binomial(2, rho_j), rho_j ~ U(0, 0.5), moved by up
+        to +-0.1 on the grid 1/denom and clamped to [0, 2]."""
+        h = C.c_void_p(None)
+        _check(lib().mih_dosage_create_synthetic(n, p, seed, int(denom), float(missing_rate), device, C.byref(h)))
+        return cls(None, denom, device=device, _handle=h)
+
+    def mu_sigma(self):
+        """mu_j (dosage units) and 1/sigma_j (1 where sigma_j = 0)."""
+        mu, s = np.empty(self.p), np.empty(self.p)
+        _check(lib().mih_snp_mu_sigma(self._h, _p(mu), _p(s)))
+        return mu, s
+
+    def export(self, col0=0, ncols=None):
+        """Numerators of columns [col0, col0 + ncols) as an n x ncols uint16 array (0xFFFF = missing)."""
+        ncols = self.p - col0 if ncols is None else ncols
+        out = np.empty((ncols, self.n), dtype=np.uint16)
+        _check(lib().mih_dosage_export(self._h, int(col0), int(ncols), _p(out)))
+        return out.T
 
 
 def _as_mat(x):
@@ -1269,9 +1332,18 @@ def _read_bim(prefix):
 
 
 def _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx=(), dosage=False, device=0):
+    """x, y, z and the variants' (chr, pos, SNPid, ref, alt) of iht / cross_validate (wrapper.jl:64-79)."""
     if str(plinkfile).endswith((".vcf", ".vcf.gz", ".bgen")):
-        raise ArgumentError("the GPU path reads binary PLINK trios; VCF / BGEN inputs are numeric matrices in the reference "
-                            "(wrapper.jl:70-71): convert them to a DenseMatrix and call fit_iht / cv_iht")
+        from .genotypes import parse_genotypes
+        if not isinstance(phenotypes, (str, os.PathLike)):
+            raise ArgumentError("VCF / BGEN inputs carry no phenotypes: give `phenotypes` as a comma-separated file, one sample "
+                                "per row (wrapper.jl:210-224)")
+        x, _ids, chrom, pos, snpid, ref, alt = parse_genotypes(plinkfile, dosage=dosage, device=device)
+        y = parse_phenotypes(plinkfile, phenotypes, d, x.n)
+        if np.shape(y)[-1] != x.n:
+            raise DimensionMismatch(f"{phenotypes} has {np.shape(y)[-1]} samples, {plinkfile} has {x.n}")
+        z = parse_covariates(covariates, exclude_std_idx) if covariates else np.ones((x.n, 1))
+        return x, y, z, (chrom, pos, snpid, ref, alt)
     for ext in (".bed", ".bim", ".fam"):
         if not os.path.exists(plinkfile + ext):
             raise ArgumentError(f"{plinkfile}{ext} not found: binary PLINK files should exclude .bim/.bed/.fam trailings and the trio "
@@ -1280,7 +1352,7 @@ def _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx=(), dosa
     x = SnpLinAlg(plinkfile + ".bed", n, center=True, scale=True, impute=True, device=device)     # wrapper.jl:68-69
     y = parse_phenotypes(plinkfile, phenotypes, d, n)
     z = parse_covariates(covariates, exclude_std_idx) if covariates else np.ones((n, 1))
-    return x, y, z
+    return x, y, z, _read_bim(plinkfile)
 
 
 def _show_result(io, res):
@@ -1314,7 +1386,7 @@ def iht(plinkfile, k, d, *, phenotypes=6, covariates="", summaryfile="iht.summar
     then overwrites the beta file with an empty CSV header, wrapper.jl:117 `CSV.write(betafile, df)` on an empty DataFrame;
     that accident is not reproduced.)"""
     d = _inst(d)
-    x, y, z = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device)
+    x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device)
     mv = _is_multivariate(y)
     user_io = kwargs.pop("io", None)
     with open(summaryfile, "w") if summaryfile else open(os.devnull, "w") as io:
@@ -1327,7 +1399,7 @@ def iht(plinkfile, k, d, *, phenotypes=6, covariates="", summaryfile="iht.summar
     if user_io is not None:
         _show_result(user_io, result)
     if betafile:
-        chrom, pos, ids, a1, a2 = _read_bim(plinkfile)
+        chrom, pos, ids, a1, a2 = info
         with open(betafile, "w") as f:
             if mv:
                 f.write("chr\tpos\tSNPid\tref\talt" + "".join(f"\tbeta_{t + 1}" for t in range(y.shape[0])) + "\n")
@@ -1356,7 +1428,7 @@ def cross_validate(plinkfile, d, *, path=range(1, 21), q=5, phenotypes=6, covari
     src/wrapper.jl:301-349 for binary PLINK input; the summary file is print_cv_results + the total time, as the reference's."""
     t0 = time.time()
     d = _inst(d)
-    x, y, z = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device)
+    x, y, z, _info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device)
     path = list(path)
     if _is_multivariate(y):
         mse = cv_iht(y, x, z.T, d=MvNormal(), path=path, q=q, **kwargs)

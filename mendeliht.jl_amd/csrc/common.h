@@ -322,6 +322,14 @@ struct mih_mat {
     int64_t   total_missing = 0;
     double   *D = nullptr;         // dense n x p (Float64 storage)
     float    *Df = nullptr;        // dense n x p (Float32 storage: `x::Matrix{Float32}`; arithmetic stays f64)
+    // dense n x p held as 16-bit dosage numerators (mih_dosage_create): d = num / denom, 0xFFFF = missing; column stride
+    // du_ld = n rounded up to 8 (the pad rows are 0xFFFF).  The matrix a fit sees is the STANDARDIZED one,
+    // x_ij = (num_ij - du_mun_j) * du_sc_j and 0 where missing (dosage_x below); mu / sinv hold mu_j and 1/sigma_j in dosage units.
+    uint16_t *Du = nullptr;
+    int64_t   du_ld = 0;
+    int32_t   denom = 0;
+    double   *du_mun = nullptr;    // p: mu_j * denom (the mean numerator)
+    double   *du_sc = nullptr;     // p: sinv_j / denom
     hipStream_t stream = nullptr;  // for the stand-alone linear-algebra entry points
     mih::DevPool *pool = nullptr;  // reserve for the fits that run on this matrix (large 2-bit matrices only)
     std::shared_ptr<mih::DevPool> pool_owner;      // a session keeps a reference: the reserve outlives a matrix destroyed first
@@ -332,6 +340,17 @@ struct mih_mat {
     mutable std::vector<hipStream_t> worker_streams;
 };
 namespace mih {
+int select_device(int device);                 // hipSetDevice after checking that the device exists (MIH_NO_DEVICE / MIH_BAD_ARG)
+
+// The 16-bit dosage storage as kernel arguments.  dosage_c: an entry centred in numerator units (0 where missing);
+// dosage_x: the entry of the standardized matrix.
+struct DosageView { const uint16_t *X; int64_t ld; const double *mun, *sc; };
+inline DosageView dosage_view(const mih_mat *h) { return {h->Du, h->du_ld, h->du_mun, h->du_sc}; }
+__device__ __forceinline__ double dosage_c(uint32_t num, double mun) { return num == 0xFFFFu ? 0.0 : (double)num - mun; }
+__device__ __forceinline__ double dosage_x(const DosageView &v, int64_t j, int64_t i)
+{
+    return dosage_c(v.X[j * v.ld + i], v.mun[j]) * v.sc[j];
+}
 constexpr int kWorkerStreamsPerLane = 4;       // the runtime maps streams onto a handful of hardware queues anyway
 // stream i of the matrix's worker set (i < 2 * kWorkerStreamsPerLane); nullptr if it cannot be created
 hipStream_t worker_stream(const mih_mat *h, int i);

@@ -53,6 +53,12 @@ __global__ void k_db_cols_dense(const T *__restrict__ D, int64_t n, const int64_
     if (i < n) panel[i + n * blockIdx.y] = (double)D[idx[blockIdx.y] * n + i];
 }
 
+__global__ void k_db_cols_dosage(DosageView dv, int64_t n, const int64_t *__restrict__ idx, double *__restrict__ panel)
+{
+    int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < n) panel[i + n * blockIdx.y] = dosage_x(dv, idx[blockIdx.y], i);
+}
+
 // GlmResp initialisation: mu = mustart(y), eta = linkfun(mu)
 __global__ void k_db_start(const double *__restrict__ y, int64_t n, int dist, int link, double *__restrict__ eta)
 {
@@ -185,7 +191,8 @@ int debias_glm_device(const mih_mat *h, const int64_t *idx_host, int64_t k64, co
             hipLaunchKernelGGL(k_db_cols_missing, dim3((unsigned)kloc), dim3(256), 0, s, idx.p, h->mu, h->sinv, h->center, h->scale,
                                h->impute, h->miss_ptr, h->miss_row, n, mine);
     } else if (kloc > 0) {
-        if (h->Df) hipLaunchKernelGGL(k_db_cols_dense<float>, dim3(nblk(n), (unsigned)kloc), dim3(256), 0, s, h->Df, n, idx.p, mine);
+        if (h->Du) hipLaunchKernelGGL(k_db_cols_dosage, dim3(nblk(n), (unsigned)kloc), dim3(256), 0, s, dosage_view(h), n, idx.p, mine);
+        else if (h->Df) hipLaunchKernelGGL(k_db_cols_dense<float>, dim3(nblk(n), (unsigned)kloc), dim3(256), 0, s, h->Df, n, idx.p, mine);
         else hipLaunchKernelGGL(k_db_cols_dense<double>, dim3(nblk(n), (unsigned)kloc), dim3(256), 0, s, h->D, n, idx.p, mine);
     }
     if (shard) MIH_TRY(shard->reduce(panel.p, n * (int64_t)k));

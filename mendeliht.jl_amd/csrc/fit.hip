@@ -28,7 +28,8 @@ int init_beta_regress_device(const mih_mat *h, const double *w_dev, const double
         hipLaunchKernelGGL(k_ib_counts, grid, dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X), h->nbp, p, M.p, cnt.p);
     } else {
         MIH_TRY(sxxd.alloc(p));
-        if (h->Df) hipLaunchKernelGGL(k_ib_dense_sxx<float>, dim3((unsigned)p), dim3(256), 0, s, h->Df, w_dev, n, p, sxxd.p);
+        if (h->Du) hipLaunchKernelGGL(k_ib_dosage_sxx, dim3((unsigned)p), dim3(256), 0, s, dosage_view(h), w_dev, n, sxxd.p);
+        else if (h->Df) hipLaunchKernelGGL(k_ib_dense_sxx<float>, dim3((unsigned)p), dim3(256), 0, s, h->Df, w_dev, n, p, sxxd.p);
         else hipLaunchKernelGGL(k_ib_dense_sxx<double>, dim3((unsigned)p), dim3(256), 0, s, h->D, w_dev, n, p, sxxd.p);
     }
     const int nsb = 64;

@@ -237,6 +237,14 @@ k_ib_dense_sxx(const T *__restrict__ D, const double *__restrict__ w, int64_t n,
     block_sum<1>(v, out + j);
 }
 static __global__ void __launch_bounds__(256)
+k_ib_dosage_sxx(DosageView dv, const double *__restrict__ w, int64_t n, double *__restrict__ out)
+{
+    int64_t j = blockIdx.x;
+    double v[1] = {0.0};
+    for (int64_t i = threadIdx.x; i < n; i += 256) { double x = dosage_x(dv, j, i); v[0] += x * x * w[i]; }
+    block_sum<1>(v, out + j);
+}
+static __global__ void __launch_bounds__(256)
 k_ib_sum(const double *__restrict__ x, int64_t p, double *__restrict__ part)
 {
     double v[1] = {0.0};

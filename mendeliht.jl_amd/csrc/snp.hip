@@ -352,6 +352,19 @@ hipStream_t worker_stream(const mih_mat *h, int i)
     return h->worker_streams[(size_t)i];
 }
 
+int select_device(int device)
+{
+    int c = 0;
+    if (hipGetDeviceCount(&c) != hipSuccess || c == 0) {
+        (void)hipGetLastError();
+        set_error("no HIP device available (the MI355X path has no CPU fallback)");
+        return MIH_NO_DEVICE;
+    }
+    if (device < 0 || device >= c) { set_error("device %d out of range (count %d)", device, c); return MIH_BAD_ARG; }
+    MIH_HIP(hipSetDevice(device));
+    return MIH_OK;
+}
+
 }  // namespace mih
 
 using namespace mih;
@@ -378,7 +391,7 @@ int mih_last_error(char *buf, size_t len)
 int mih_version(int *major, int *minor)
 {
     if (major) *major = 0;
-    if (minor) *minor = 4;        // round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
+    if (minor) *minor = 5;        // 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
     return MIH_OK;
 }
 
@@ -388,19 +401,6 @@ int mih_abi_sizes(int64_t *sizes, int32_t n)
                           (int64_t)sizeof(mih_comm)};
     if (!sizes) return MIH_BAD_ARG;
     for (int i = 0; i < n && i < 4; ++i) sizes[i] = v[i];
-    return MIH_OK;
-}
-
-static int select_device(int device)
-{
-    int c = 0;
-    if (hipGetDeviceCount(&c) != hipSuccess || c == 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available (the MI355X path has no CPU fallback)");
-        return MIH_NO_DEVICE;
-    }
-    if (device < 0 || device >= c) { set_error("device %d out of range (count %d)", device, c); return MIH_BAD_ARG; }
-    MIH_HIP(hipSetDevice(device));
     return MIH_OK;
 }
 
@@ -662,6 +662,9 @@ int mih_mat_destroy(mih_mat *h)
     if (h->miss_row) (void)hipFree(h->miss_row);
     if (h->D) (void)hipFree(h->D);
     if (h->Df) (void)hipFree(h->Df);
+    if (h->Du) (void)hipFree(h->Du);
+    if (h->du_mun) (void)hipFree(h->du_mun);
+    if (h->du_sc) (void)hipFree(h->du_sc);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;                                  // the reserve goes with its last owner (pool_owner)
     return MIH_OK;
@@ -689,7 +692,7 @@ int mih_mat_dims(const mih_mat *h, int64_t *n, int64_t *p)
 
 int mih_snp_mu_sigma(const mih_mat *h, double *mu, double *sinv)
 {
-    if (!h || h->kind != 0) { set_error("not a SnpLinAlg handle"); return MIH_BAD_ARG; }
+    if (!h || (h->kind != 0 && !h->Du)) { set_error("not a SnpLinAlg or dosage handle"); return MIH_BAD_ARG; }
     MIH_HIP(hipSetDevice(h->device));
     if (mu) MIH_HIP(hipMemcpy(mu, h->mu, sizeof(double) * (size_t)h->p, hipMemcpyDeviceToHost));
     if (sinv) MIH_HIP(hipMemcpy(sinv, h->sinv, sizeof(double) * (size_t)h->p, hipMemcpyDeviceToHost));

@@ -1407,6 +1407,128 @@ static void launch_dense_lds(const T *D, const mih_mat *h, const double *r_dev, 
         hipLaunchKernelGGL((k_xtv_dense_lds<T, 1>), grid, block, 0, s, D, h->n, h->p, r_dev + (int64_t)v * h->n, out_dev + (int64_t)v * h->p);
 }
 
+// The 16-bit dosage image (mih_dosage_create): out_j = sc_j * sum_i c_ij r_i with c_ij = num_ij - mun_j (0 where missing,
+// pad rows included), the centring done per entry in numerator units before the product -- folding the mean out as
+// sc_j (sum num r - mun_j sum r) cancels badly for a mean near 2.  Eight waves per block, two columns per wave (16 columns
+// per block); a step is two 16-B loads (8 rows each) per lane and column, 1024 rows.  The residual chunk of a step is
+// staged once per block in LDS, double buffered, as 16-B pairs in the order the lanes read them (pair 4 L + h of the
+// step at h * 128 + L, L = lane + 64 u: conflict-free ds_read_b128; the coalesced global read of pair tid pays a
+// 4-way conflict on the one write per step instead), and one read serves both columns of a wave.
+// LDS: 2 * NRHS * 512 * 16 B = 16 KiB per residual, so NRHS <= 4 (64 KiB).  Per (column, residual) the chains and the
+// final tree are those of NRHS = 1: fused and single passes give the same bits; any n (the pad rows are missing).
+constexpr int kDsgWaves = 8, kDsgCols = 2, kDsgU = 2;
+constexpr int kDsgPairs = kDsgU * 64 * 4;                 // f64x2 residual pairs per step
+template <int NRHS>
+__global__ void __launch_bounds__(512)
+k_xtv_dosage_lds(DosageView dv, int64_t n, int64_t p, const double *__restrict__ r, double *__restrict__ out)
+{
+    constexpr int CW = kDsgWaves * kDsgCols;
+    __shared__ f64x2 rt[2][NRHS][kDsgPairs];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t jj[kDsgCols], j[kDsgCols];
+    const u32x4 *cx[kDsgCols];
+    double mun[kDsgCols];
+    #pragma unroll
+    for (int c = 0; c < kDsgCols; ++c) {
+        jj[c] = blockIdx.x * (int64_t)CW + wave * kDsgCols + c;
+        j[c] = jj[c] < p ? jj[c] : p - 1;                   // idle columns redo the last one
+        cx[c] = reinterpret_cast<const u32x4 *>(dv.X + j[c] * dv.ld);
+        mun[c] = dv.mun[j[c]];
+    }
+    const int64_t nv = dv.ld / 8, steps = (nv + 64 * kDsgU - 1) / (64 * kDsgU);
+    const u32x4 vmiss = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    // this thread stages pair tid of each step (rows 2 tid, 2 tid + 1) at LDS slot (tid & 3) * 128 + (tid >> 2)
+    const int64_t trow = 2 * (int64_t)threadIdx.x;
+    const int slot = (threadIdx.x & 3) * (kDsgPairs / 4) + (threadIdx.x >> 2);
+    auto stage = [&](int64_t st, int v) -> f64x2 {
+        const int64_t i = st * 2 * kDsgPairs + trow;
+        const double *rv = r + (int64_t)v * n;
+        f64x2 q; q.x = i < n ? rv[i] : 0.0; q.y = i + 1 < n ? rv[i + 1] : 0.0;
+        return q;
+    };
+    double a[NRHS][kDsgCols][4];
+    #pragma unroll
+    for (int v = 0; v < NRHS; ++v)
+        #pragma unroll
+        for (int c = 0; c < kDsgCols; ++c)
+            #pragma unroll
+            for (int e = 0; e < 4; ++e) a[v][c][e] = 0.0;
+    #pragma unroll
+    for (int v = 0; v < NRHS; ++v) rt[0][v][slot] = stage(0, v);
+    __syncthreads();
+    u32x4 x[kDsgCols][kDsgU], xn[kDsgCols][kDsgU];
+    #pragma unroll
+    for (int c = 0; c < kDsgCols; ++c)
+        #pragma unroll
+        for (int u = 0; u < kDsgU; ++u) { const int64_t i = lane + 64 * u; x[c][u] = i < nv ? __builtin_nontemporal_load(cx[c] + i) : vmiss; }
+    for (int64_t st = 0; st < steps; ++st) {
+        const int buf = (int)(st & 1);
+        f64x2 rn[NRHS];
+        #pragma unroll
+        for (int v = 0; v < NRHS; ++v) rn[v] = stage(st + 1, v);
+        #pragma unroll
+        for (int c = 0; c < kDsgCols; ++c)
+            #pragma unroll
+            for (int u = 0; u < kDsgU; ++u) {
+                const int64_t i = (st + 1) * 64 * kDsgU + lane + 64 * u;
+                xn[c][u] = i < nv ? __builtin_nontemporal_load(cx[c] + i) : vmiss;
+            }
+        #pragma unroll
+        for (int u = 0; u < kDsgU; ++u) {
+            double cv[kDsgCols][8];
+            #pragma unroll
+            for (int c = 0; c < kDsgCols; ++c) {
+                const uint32_t w[4] = {x[c][u].x, x[c][u].y, x[c][u].z, x[c][u].w};
+                #pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    cv[c][2 * k] = dosage_c(w[k] & 0xFFFFu, mun[c]);
+                    cv[c][2 * k + 1] = dosage_c(w[k] >> 16, mun[c]);
+                }
+            }
+            #pragma unroll
+            for (int v = 0; v < NRHS; ++v)
+                #pragma unroll
+                for (int hh = 0; hh < 4; ++hh) {
+                    const f64x2 rv = rt[buf][v][hh * (kDsgPairs / 4) + lane + 64 * u];
+                    #pragma unroll
+                    for (int c = 0; c < kDsgCols; ++c) {
+                        a[v][c][2 * (hh & 1)] = fma(cv[c][2 * hh], rv.x, a[v][c][2 * (hh & 1)]);
+                        a[v][c][2 * (hh & 1) + 1] = fma(cv[c][2 * hh + 1], rv.y, a[v][c][2 * (hh & 1) + 1]);
+                    }
+                }
+        }
+        #pragma unroll
+        for (int v = 0; v < NRHS; ++v) rt[buf ^ 1][v][slot] = rn[v];
+        __syncthreads();
+        #pragma unroll
+        for (int c = 0; c < kDsgCols; ++c)
+            #pragma unroll
+            for (int u = 0; u < kDsgU; ++u) x[c][u] = xn[c][u];
+    }
+    #pragma unroll
+    for (int v = 0; v < NRHS; ++v)
+        #pragma unroll
+        for (int c = 0; c < kDsgCols; ++c) {
+            const double sum = wave_sum((a[v][c][0] + a[v][c][1]) + (a[v][c][2] + a[v][c][3]));
+            if (lane == 0 && jj[c] < p) out[(int64_t)v * p + j[c]] = sum * dv.sc[j[c]];
+        }
+}
+
+static void launch_dosage_lds(const mih_mat *h, const double *r_dev, int m, double *out_dev, hipStream_t s)
+{
+    const dim3 grid((unsigned)((h->p + kDsgWaves * kDsgCols - 1) / (kDsgWaves * kDsgCols))), block(64 * kDsgWaves);
+    const DosageView dv = dosage_view(h);
+    int v = 0;
+    for (; v + 4 <= m; v += 4)
+        hipLaunchKernelGGL((k_xtv_dosage_lds<4>), grid, block, 0, s, dv, h->n, h->p, r_dev + (int64_t)v * h->n, out_dev + (int64_t)v * h->p);
+    if (m - v >= 2) {
+        hipLaunchKernelGGL((k_xtv_dosage_lds<2>), grid, block, 0, s, dv, h->n, h->p, r_dev + (int64_t)v * h->n, out_dev + (int64_t)v * h->p);
+        v += 2;
+    }
+    if (m - v == 1)
+        hipLaunchKernelGGL((k_xtv_dosage_lds<1>), grid, block, 0, s, dv, h->n, h->p, r_dev + (int64_t)v * h->n, out_dev + (int64_t)v * h->p);
+}
+
 constexpr int kMaxSplits = 16;
 constexpr int kStatBlocks = 64;
 
@@ -1604,6 +1726,18 @@ void xtv_count_peels(const mih_mat *h, XtvWork &w, hipStream_t s)
 int xtv_device(const mih_mat *h, XtvWork &w, const double *r_dev, int m, double *out_dev, hipStream_t s)
 {
     const XtvTune &tn = w.tune;
+    if (h->kind == 1 && h->Du) {                 // (any n, any alignment: no fallback kernel)
+        PassRecord rec;
+        const bool prof = prof_begin(h, s, rec);
+        launch_dosage_lds(h, r_dev, m, out_dev, s);
+        if (prof) {
+            rec.residuals = m; rec.operands = m; rec.stream_tag = w.stream_tag;
+            snprintf(rec.kernel, sizeof(rec.kernel), "k_xtv_dosage_lds<u16>");
+            prof_end(h, s, rec);
+        }
+        MIH_HIP(hipGetLastError());
+        return MIH_OK;
+    }
     if (h->kind == 1) {
         const bool lds_ok = tn.variant < 0 && (((uintptr_t)(h->Df ? (const void *)h->Df : (const void *)h->D)) & 15) == 0
                             && h->n % (h->Df ? 4 : 2) == 0;
@@ -1813,7 +1947,7 @@ int mih_xtv_algorithmic_bytes(const mih_mat *h, int m, double *bytes)
     if (h->kind == 0)
         *bytes = (double)h->p * (double)((h->n + 3) / 4) + 8.0 * m * ((double)h->n + (double)h->p) + 16.0 * (double)h->p;
     else
-        *bytes = (h->Df ? 4.0 : 8.0) * (double)h->n * (double)h->p + 8.0 * m * ((double)h->n + (double)h->p);
+        *bytes = (h->Du ? 2.0 : h->Df ? 4.0 : 8.0) * (double)h->n * (double)h->p + 8.0 * m * ((double)h->n + (double)h->p);
     return MIH_OK;
 }
 

@@ -371,6 +371,20 @@ k_xv_dense(const T *__restrict__ D, int64_t n, const int64_t *__restrict__ idx,
     partial[(int64_t)g * n_pad + i] = acc;
 }
 
+__global__ void __launch_bounds__(256)
+k_xv_dosage(DosageView dv, int64_t n, const int64_t *__restrict__ idx, const double *__restrict__ val, int64_t nnz, int groups,
+            int64_t n_pad, double *__restrict__ partial)
+{
+    int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    int g = blockIdx.y;
+    if (i >= n) return;
+    int64_t per = (nnz + groups - 1) / groups;
+    int64_t t0 = g * per, t1 = t0 + per < nnz ? t0 + per : nnz;
+    double acc = 0.0;
+    for (int64_t t = t0; t < t1; ++t) acc = fma(dosage_x(dv, idx[t], i), val[t], acc);
+    partial[(int64_t)g * n_pad + i] = acc;
+}
+
 __global__ void k_xv_reduce(const double *__restrict__ partial, int groups, int64_t n_pad, int64_t n,
                             int clamp20, double *__restrict__ out)
 {
@@ -530,7 +544,9 @@ int xv_sparse_device(const mih_mat *h, XvWork &w, const int64_t *idx_dev, const 
             if (clamp20) hipLaunchKernelGGL(k_clamp20, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, out_dev, h->n);
         }
     } else {
-        if (h->Df) hipLaunchKernelGGL(k_xv_dense<float>, dim3((unsigned)((h->n + 255) / 256), groups), dim3(256), 0, s, h->Df, h->n, idx_dev, val_dev,
+        if (h->Du) hipLaunchKernelGGL(k_xv_dosage, dim3((unsigned)((h->n + 255) / 256), groups), dim3(256), 0, s, dosage_view(h), h->n, idx_dev,
+                                      val_dev, nnz, groups, np, w.partial.p);
+        else if (h->Df) hipLaunchKernelGGL(k_xv_dense<float>, dim3((unsigned)((h->n + 255) / 256), groups), dim3(256), 0, s, h->Df, h->n, idx_dev, val_dev,
                                       nnz, groups, np, w.partial.p);
         else hipLaunchKernelGGL(k_xv_dense<double>, dim3((unsigned)((h->n + 255) / 256), groups), dim3(256), 0, s, h->D, h->n, idx_dev, val_dev,
                                 nnz, groups, np, w.partial.p);

@@ -1,0 +1,288 @@
+"""VCF and BGEN genotype readers -- parse_genotypes (src/wrapper.jl:360-485) for the GPU path.
+
+The reference decodes VCF / BGEN genotypes into a dense Matrix{Float64}.  Real dosages sit on a small integer grid (hard
+calls: num / 1; VCF DS with q decimals: num / 10^q; BGEN with B-bit probabilities: num / (2^B - 1)), so the readers keep the
+exact numerators and one common denominator, reduced by their gcd: with denom <= 32767 the matrix goes to the device as a
+DosageMatrix (16 bits per entry, the same values); otherwise as a DenseMatrix of the standardized f64 values, with a warning.
+"""
+import gzip
+import math
+import os
+import struct
+import warnings
+import zlib
+from fractions import Fraction
+
+import numpy as np
+
+from .api import ArgumentError, DenseMatrix, DimensionMismatch, DosageMatrix, SnpLinAlg, _count_lines, _read_bim
+
+MAX_DENOM = 32767
+MISSING = 0xFFFF
+
+
+# ---- the grid ----------------------------------------------------------------------------------
+def _reduce(num, den):
+    """num (int64, -1 = missing) / den reduced by the gcd of den and every numerator."""
+    g = den
+    for v in np.unique(num[num > 0]):
+        g = math.gcd(g, int(v))
+        if g == 1:
+            break
+    if g > 1:
+        num = np.where(num >= 0, num // g, -1)
+    return num, den // g
+
+
+def _to_u16(num):
+    return np.where(num < 0, MISSING, num).astype(np.uint16)
+
+
+def dosage_grid(d):
+    """Float dosages (NaN = missing) -> (uint16 numerators, denom): the smallest grid among hard calls, up to 4 decimals and
+    B <= 15 bit probabilities that holds every value, reduced by the gcd.  ArgumentError if there is none."""
+    d = np.asarray(d, dtype=np.float64)
+    if d.ndim != 2:
+        raise DimensionMismatch("dosages must be a matrix")
+    ok = ~np.isnan(d)
+    v = d[ok]
+    if v.size and (v.min() < 0.0 or v.max() > 2.0):
+        raise ArgumentError("dosages must lie in [0, 2]")
+    for den in sorted({1, 10, 100, 1000, 10000} | {(1 << b) - 1 for b in range(2, 16)}):
+        q = v * den
+        k = np.rint(q)
+        if np.all(np.abs(q - k) <= 1e-7):
+            num = np.full(d.shape, -1, dtype=np.int64)
+            num[ok] = k.astype(np.int64)
+            num, den = _reduce(num, den)
+            return _to_u16(num), den
+    raise ArgumentError("the dosages sit on no grid num / denom with denom <= 32767 (hard calls, up to 4 decimals, "
+                        "B <= 15 bit probabilities): use a DenseMatrix")
+
+
+def standardize_dosages(d):
+    """standardize_genotypes! (wrapper.jl:406-423) in numpy, NaN = missing (imputed by the mean, i.e. 0 after centring)."""
+    d = np.array(d, dtype=np.float64)
+    for j in range(d.shape[1]):
+        c = d[:, j]
+        ok = ~np.isnan(c)
+        m = c[ok].sum() / ok.sum() if ok.any() else 0.0
+        s = math.sqrt(m * (1.0 - m / 2.0))
+        c[~ok] = m
+        c -= m
+        if s > 0:
+            c /= s
+    return d
+
+
+def _combine(cols):
+    """Columns of (int64 numerators, -1 = missing; denominator) -> (n x p int64 numerators, common denominator) reduced, or
+    None when the common denominator is beyond int64 arithmetic."""
+    den = 1
+    for _, q in cols:
+        den = den * q // math.gcd(den, q)
+        if den > (1 << 40):
+            return None
+    num = np.empty((cols[0][0].size if cols else 0, len(cols)), dtype=np.int64, order="F")
+    for j, (c, q) in enumerate(cols):
+        num[:, j] = np.where(c >= 0, c * (den // q), -1)
+    return _reduce(num, den)
+
+
+def genotype_values(cols):
+    """Columns of (numerators, denom) -> (uint16 numerators, denom) on their common reduced grid, or (None, the standardized
+    Float64 matrix) with a warning when that grid is finer than 1/32767 (e.g. 16-bit BGEN with fractional probabilities)."""
+    got = _combine(cols)
+    if got is not None and got[1] <= MAX_DENOM:
+        return _to_u16(got[0]), got[1]
+    d = np.empty((cols[0][0].size, len(cols)), order="F")
+    for j, (c, q) in enumerate(cols):
+        d[:, j] = np.where(c >= 0, c / q, np.nan)
+    warnings.warn("the genotypes sit on no grid num / denom with denom <= 32767: stored as a dense Float64 matrix "
+                  "(8 bytes per entry)", stacklevel=3)
+    return None, standardize_dosages(d)
+
+
+# ---- VCF ---------------------------------------------------------------------------------------
+def _gt_count(tok):
+    """ALT allele count of a GT value ("0/1", "1|1", "./." missing)."""
+    a = tok.replace("|", "/").split("/")
+    if "." in a or tok == "":
+        return -1
+    return sum(x != "0" for x in a)
+
+
+def _ds_frac(tok):
+    if tok in (".", ""):
+        return None
+    try:
+        return Fraction(tok)
+    except ValueError:
+        raise ArgumentError(f"unreadable DS value {tok!r}") from None
+
+
+def read_vcf(path, dosage=False):
+    """(columns of (numerators, denom), sample ids, chr, pos, ids, ref, alt) of a VCF (`.vcf` or `.vcf.gz`): GT as ALT allele
+    counts (denom 1), or the DS field with dosage=True (its decimals exactly)."""
+    opener = gzip.open if str(path).endswith(".gz") else open
+    field = "DS" if dosage else "GT"
+    samples, cols, chrom, pos, ids, ref, alt = None, [], [], [], [], [], []
+    with opener(path, "rt") as f:
+        for line in f:
+            if line.startswith("##"):
+                continue
+            t = line.rstrip("\n").split("\t")
+            if line.startswith("#"):
+                samples = t[9:]
+                continue
+            if samples is None:
+                raise ArgumentError(f"{path}: no #CHROM header line")
+            if len(t) != 9 + len(samples):
+                raise DimensionMismatch(f"{path}: record {len(cols) + 1} has {len(t) - 9} samples, the header {len(samples)}")
+            if "," in t[4]:
+                raise ArgumentError(f"{path}: record {len(cols) + 1} ({t[2]}) is multi-allelic; only biallelic records are supported")
+            fmt = t[8].split(":")
+            if field not in fmt:
+                raise ArgumentError(f"{path}: record {len(cols) + 1} has no {field} field")
+            k = fmt.index(field)
+            vals = [s.split(":")[k] if s.count(":") >= k else "." for s in t[9:]]
+            if dosage:
+                fr = [_ds_frac(v) for v in vals]
+                if any(x is not None and x < 0 for x in fr):
+                    raise ArgumentError(f"{path}: record {len(cols) + 1} has a negative DS value")
+                den = 1
+                for x in fr:
+                    if x is not None:
+                        den = den * x.denominator // math.gcd(den, x.denominator)
+                c = np.array([-1 if x is None else x.numerator * (den // x.denominator) for x in fr], dtype=np.int64)
+                if (c > 2 * den).any():
+                    raise ArgumentError(f"{path}: record {len(cols) + 1} has a DS value above 2")
+            else:
+                c, den = np.array([_gt_count(v) for v in vals], dtype=np.int64), 1
+            cols.append((c, den))
+            chrom.append(t[0]); pos.append(int(t[1])); ids.append(t[2]); ref.append(t[3]); alt.append(t[4])
+    if samples is None:
+        raise ArgumentError(f"{path}: no #CHROM header line")
+    return cols, samples, chrom, pos, ids, ref, alt
+
+
+# ---- BGEN v1.2 ---------------------------------------------------------------------------------
+def _u(fmt, b, off):
+    return struct.unpack_from(fmt, b, off)[0]
+
+
+def _bgen_str(b, off, width):
+    n = _u("<H" if width == 2 else "<I", b, off)
+    return b[off + width:off + width + n].decode(), off + width + n
+
+
+def read_bgen(path, sample_path=None):
+    """(columns of (numerators, denom), sample ids, chr, pos, ids, ref, alt) of a BGEN v1.2 file, layout 2, compression none
+    or zlib, unphased diploid biallelic: d = (2 k_BB + k_AB) / (2^B - 1), the ALT (second) allele counted as
+    second_dosage! does (wrapper.jl:381).  Sample ids from `sample_path` (default: the .sample file beside the .bgen), else
+    the file's own sample block, else 1..N."""
+    with open(path, "rb") as f:
+        b = f.read()
+    off, lh, m, n = _u("<I", b, 0), _u("<I", b, 4), _u("<I", b, 8), _u("<I", b, 12)
+    if b[16:20] not in (b"bgen", b"\0\0\0\0"):
+        raise ArgumentError(f"{path} is not a BGEN file")
+    flags = _u("<I", b, 4 + lh - 4)
+    comp, layout = flags & 3, (flags >> 2) & 15
+    if comp == 2:
+        raise ArgumentError(f"{path}: zstd-compressed BGEN is not supported (compression none or zlib only)")
+    if comp not in (0, 1):
+        raise ArgumentError(f"{path}: unknown BGEN compression {comp}")
+    if layout != 2:
+        raise ArgumentError(f"{path}: BGEN layout {layout} is not supported (layout 2 only)")
+    samples = None
+    if flags >> 31:
+        q, pos_ = _u("<I", b, 4 + lh + 4), 4 + lh + 8
+        samples = []
+        for _ in range(q):
+            s, pos_ = _bgen_str(b, pos_, 2)
+            samples.append(s)
+    if sample_path is None and os.path.isfile(str(path)[:-5] + ".sample"):
+        sample_path = str(path)[:-5] + ".sample"
+    if sample_path is not None:
+        with open(sample_path) as f:
+            rows = [ln.split() for ln in f if ln.strip()][2:]       # header and type lines
+        samples = [r[0] for r in rows]
+    if samples is None:
+        samples = [str(i + 1) for i in range(n)]
+    if len(samples) != n:
+        raise DimensionMismatch(f"{path}: {len(samples)} sample ids for N = {n}")
+    cols, chrom, pos, ids, ref, alt = [], [], [], [], [], []
+    p_ = off + 4
+    for v in range(m):
+        _vid, p_ = _bgen_str(b, p_, 2)
+        rsid, p_ = _bgen_str(b, p_, 2)
+        ch, p_ = _bgen_str(b, p_, 2)
+        vpos, k = _u("<I", b, p_), _u("<H", b, p_ + 4)
+        p_ += 6
+        alleles = []
+        for _ in range(k):
+            a, p_ = _bgen_str(b, p_, 4)
+            alleles.append(a)
+        if k != 2:
+            raise ArgumentError(f"{path}: marker {v + 1} of BGEN is not biallelic!")
+        clen = _u("<I", b, p_)
+        blk = b[p_ + 4:p_ + 4 + clen]
+        p_ += 4 + clen
+        if comp == 1:
+            dlen = _u("<I", blk, 0)
+            blk = zlib.decompress(blk[4:])
+            if len(blk) != dlen:
+                raise ArgumentError(f"{path}: marker {v + 1}: corrupt genotype block")
+        nn, kk, pmin, pmax = _u("<I", blk, 0), _u("<H", blk, 4), blk[6], blk[7]
+        if nn != n or kk != 2:
+            raise ArgumentError(f"{path}: marker {v + 1}: genotype block disagrees with the header")
+        ploidy = np.frombuffer(blk, dtype=np.uint8, count=n, offset=8)
+        if pmin != 2 or pmax != 2 or ((ploidy & 0x3F) != 2).any():
+            raise ArgumentError(f"{path}: marker {v + 1}: ploidy other than 2 is not supported")
+        phased, nbits = blk[8 + n], blk[9 + n]
+        if phased:
+            raise ArgumentError(f"{path}: marker {v + 1}: phased BGEN data is not supported")
+        if not 1 <= nbits <= 32:
+            raise ArgumentError(f"{path}: marker {v + 1}: {nbits} bits per probability")
+        nb = (2 * n * nbits + 7) // 8
+        bits = np.unpackbits(np.frombuffer(blk, dtype=np.uint8, count=nb, offset=10 + n), bitorder="little")
+        vals = bits[:2 * n * nbits].reshape(2 * n, nbits).astype(np.int64) @ (np.int64(1) << np.arange(nbits, dtype=np.int64))
+        full = (1 << nbits) - 1
+        k_aa, k_ab = vals[0::2], vals[1::2]
+        k_bb = full - k_aa - k_ab
+        miss = (ploidy & 0x80) != 0
+        if (k_bb[~miss] < 0).any():
+            raise ArgumentError(f"{path}: marker {v + 1}: probabilities sum above 1")
+        cols.append((np.where(miss, -1, 2 * k_bb + k_ab), full))
+        chrom.append(ch); pos.append(vpos); ids.append(rsid); ref.append(alleles[0]); alt.append(alleles[1])
+    return cols, samples, chrom, pos, ids, ref, alt
+
+
+# ---- parse_genotypes ---------------------------------------------------------------------------
+def parse_genotypes(tgtfile, dosage=False, device=0):
+    """parse_genotypes(tgtfile, dosage) -- wrapper.jl:451-485: (X, sample_ids, chr, pos, snpid, ref, alt).  VCF (`.vcf`,
+    `.vcf.gz`; GT allele counts, or DS with dosage=True) and BGEN (`.bgen`) give a DosageMatrix (or, on a grid finer than
+    1/32767, a DenseMatrix of the standardized values); a binary PLINK trio (the path without .bed/.bim/.fam) gives
+    SnpLinAlg(center=true, scale=true, impute=true).  Either way X is the standardized matrix the reference fits."""
+    tgt = str(tgtfile)
+    if tgt.endswith((".vcf", ".vcf.gz")):
+        cols, samples, chrom, pos, ids, ref, alt = read_vcf(tgt, dosage)
+    elif tgt.endswith(".bgen"):
+        cols, samples, chrom, pos, ids, ref, alt = read_bgen(tgt)
+    elif all(os.path.isfile(tgt + e) for e in (".bed", ".bim", ".fam")):
+        if dosage:
+            raise ArgumentError("PLINK files detected but dosage = true!")
+        n = _count_lines(tgt + ".fam")
+        with open(tgt + ".fam") as f:
+            samples = [ln.split()[1] for ln in f if ln.strip()]
+        chrom, pos, ids, a1, a2 = _read_bim(tgt)
+        x = SnpLinAlg(tgt + ".bed", n, center=True, scale=True, impute=True, device=device)
+        return x, samples, chrom, [int(q) for q in pos], ids, a1, a2
+    else:
+        raise ArgumentError("Unrecognized target file format: target file can only be VCF files (ends in .vcf or .vcf.gz), "
+                            "BGEN (ends in .bgen) or PLINK (do not include.bim/bed/fam) and all trio must exist in 1 directory)")
+    if not cols:
+        raise ArgumentError(f"{tgt} holds no variants")
+    num, val = genotype_values(cols)
+    x = DenseMatrix(val, device=device) if num is None else DosageMatrix(num, val, device=device)
+    return x, samples, chrom, pos, ids, ref, alt
