@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -97,6 +97,34 @@ int mih_dosage_create(const uint16_t *num, int64_t n, int64_t p, int64_t col_str
  * rho_j ~ U(0, 0.5), moved by up to +-0.1 on the grid of denom and clamped to [0, 2]; each entry missing with
  * probability missing_rate. */
 int mih_dosage_create_synthetic(int64_t n, int64_t p, uint64_t seed, int32_t denom, double missing_rate, int device, mih_mat **out);
+/* A dosage handle built straight from a BGEN v1.2 file: the n x ncols matrix of the genotype blocks whose 4-byte length fields
+ * sit at the file offsets block_offset[0 .. ncols) (increasing), as the caller's walk of the variant headers found them:
+ * consecutive variants are read in runs of a few MB, offsets that skip variants block by block (no skipped block is read).
+ * Accepted: layout 2, compression 0 (none) or 1 (zlib), unphased, every sample diploid, the same B in 1..16 bits per
+ * probability in every block.  Dosage d = (2 k_BB + k_AB) / (2^B - 1) (the ALT allele counted), 0xFFFF where the ploidy byte
+ * marks the sample missing; the result is on the matrix's own reduced grid -- numerators and *denom_out as
+ * genotypes.genotype_values gives them for these columns.  threads = 0: the library's default (at most 8 workers).
+ * On a block that is refused or cannot stream: MIH_BAD_ARG, nothing allocated, *bad_block the first such block in file order
+ * (0-based among the ncols) and *bad_what why (MIH_BGEN_*).  Codes 1-6 are read_bgen's refusals, by its order within a block;
+ * 10-13 mark a file that does not fit this path (a reader falls back to its general one there). */
+enum {
+    MIH_BGEN_CORRUPT = 1,       /* the inflated length is not the stored one */
+    MIH_BGEN_HEADER = 2,        /* N or K of the block disagrees with the file header (K != 2: not biallelic) */
+    MIH_BGEN_PLOIDY = 3,        /* pmin, pmax or a sample's ploidy other than 2 */
+    MIH_BGEN_PHASED = 4,        /* phased data */
+    MIH_BGEN_BITS = 5,          /* B outside 1..32 */
+    MIH_BGEN_SUM = 6,           /* a non-missing sample's probabilities sum above 1 */
+    MIH_BGEN_DEEP = 10,         /* B above 16 */
+    MIH_BGEN_MIXED = 11,        /* B differs from the first block's */
+    MIH_BGEN_FINE = 12,         /* 16 bits whose reduced denominator is above 32767 (fractional dosages) */
+    MIH_BGEN_MALFORMED = 13     /* a block too short for what it holds, or a zlib stream that does not inflate */
+};
+int mih_dosage_create_bgen(const char *path, int64_t n, int64_t ncols, const int64_t *block_offset, int compression,
+                           int threads, int device, mih_mat **out, int32_t *denom_out, int64_t *bad_block, int32_t *bad_what);
+/* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
+ * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
+ * while a fit uses the handle. */
+int mih_dosage_regrid(mih_mat *h, int32_t denom);
 /* Numerators of columns [col0, col0 + ncols) of a dosage handle into out (n x ncols column-major, 0xFFFF = missing). */
 int mih_dosage_export(const mih_mat *h, int64_t col0, int64_t ncols, uint16_t *out);
 /* Releases the matrix.  A mih_session must not be stepped after its matrix is gone, but it may be destroyed later: the

@@ -149,6 +149,9 @@ def lib():
         "mih_dosage_create": [vp, i64, i64, i64, i32, C.c_int, C.POINTER(vp)],
         "mih_dosage_create_synthetic": [i64, i64, C.c_uint64, i32, dbl, C.c_int, C.POINTER(vp)],
         "mih_dosage_export": [vp, i64, i64, vp],
+        "mih_dosage_create_bgen": [C.c_char_p, i64, i64, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64),
+                                   C.POINTER(i32)],
+        "mih_dosage_regrid": [vp, i32],
         "mih_mat_destroy": [vp],
         "mih_mat_dims": [vp, C.POINTER(i64), C.POINTER(i64)],
         "mih_mat_reserve": [vp, i64],
@@ -205,7 +208,8 @@ def exported_symbols():
     return ["mih_device_count", "mih_last_error", "mih_version", "mih_snp_create", "mih_snp_create_synthetic",
             "mih_snp_create_synthetic_shard",
             "mih_dense_create", "mih_dense_create_synthetic", "mih_dense_create_f32",
-            "mih_dosage_create", "mih_dosage_create_synthetic", "mih_dosage_export", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
+            "mih_dosage_create", "mih_dosage_create_synthetic", "mih_dosage_export",
+            "mih_dosage_create_bgen", "mih_dosage_regrid", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
@@ -587,6 +591,13 @@ class DosageMatrix(_Mat):
         mu, s = np.empty(self.p), np.empty(self.p)
         _check(lib().mih_snp_mu_sigma(self._h, _p(mu), _p(s)))
         return mu, s
+
+    def regrid(self, denom):
+        """The same matrix over the finer grid 1 / denom (a multiple of self.denom, at most 32767): every numerator times
+        denom / self.denom, the column statistics recomputed.  Column shards agree on one denominator this way."""
+        _check(lib().mih_dosage_regrid(self._h, int(denom)))
+        self.denom = int(denom)
+        return self
 
     def export(self, col0=0, ncols=None):
         """Numerators of columns [col0, col0 + ncols) as an n x ncols uint16 array (0xFFFF = missing)."""

@@ -345,6 +345,11 @@ int select_device(int device);                 // hipSetDevice after checking th
 // The 16-bit dosage storage as kernel arguments.  dosage_c: an entry centred in numerator units (0 where missing);
 // dosage_x: the entry of the standardized matrix.
 struct DosageView { const uint16_t *X; int64_t ld; const double *mun, *sc; };
+// dosage.hip: storage and statistics of an n x p dosage handle, and the multiply that moves columns to a finer grid (the BGEN
+// reader's fix-up and mih_dosage_regrid): column j times gcol[j] / g (gcol != nullptr), else times mult; missing entries stay
+int dosage_alloc(mih_mat *h, int64_t n, int64_t p, int32_t denom, int device);
+int dosage_stats(mih_mat *h);
+void dosage_rescale(mih_mat *h, const uint32_t *gcol, uint32_t g, uint32_t mult);
 inline DosageView dosage_view(const mih_mat *h) { return {h->Du, h->du_ld, h->du_mun, h->du_sc}; }
 __device__ __forceinline__ double dosage_c(uint32_t num, double mun) { return num == 0xFFFFu ? 0.0 : (double)num - mun; }
 __device__ __forceinline__ double dosage_x(const DosageView &v, int64_t j, int64_t i)

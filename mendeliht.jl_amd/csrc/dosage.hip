@@ -93,7 +93,7 @@ k_dosage_synth(uint16_t *__restrict__ X, int64_t ld, int64_t n, int64_t p, uint6
 }
 
 // allocate the storage and statistics of an n x p dosage matrix (kind 1, no centring flags: the storage standardizes)
-static int dosage_alloc(mih_mat *h, int64_t n, int64_t p, int32_t denom, int device)
+int dosage_alloc(mih_mat *h, int64_t n, int64_t p, int32_t denom, int device)
 {
     h->kind = 1; h->device = device; h->n = n; h->p = p; h->center = h->scale = h->impute = 0;
     h->denom = denom;
@@ -108,7 +108,7 @@ static int dosage_alloc(mih_mat *h, int64_t n, int64_t p, int32_t denom, int dev
 }
 
 // column statistics; MIH_BAD_ARG if a numerator other than 0xFFFF exceeds 2 denom
-static int dosage_stats(mih_mat *h)
+int dosage_stats(mih_mat *h)
 {
     DevBuf<unsigned long long> bad;
     MIH_TRY(bad.alloc(1));
@@ -120,6 +120,32 @@ static int dosage_stats(mih_mat *h)
     MIH_HIP(hipStreamSynchronize(h->stream));
     if (nbad) { set_error("%llu dosage numerators exceed 2 * denom = %d (0xFFFF marks a missing entry)", nbad, 2 * h->denom); return MIH_BAD_ARG; }
     return MIH_OK;
+}
+
+// Column j of the numerators times m_j = gcol[j] / g (the BGEN reader's fix-up onto the common grid) or times mult (regrid):
+// a value v / denom becomes (v m) / (denom m), exactly; 0xFFFF stays missing.  One block per column, 8 rows per thread.
+__global__ void __launch_bounds__(256)
+k_dosage_scale(uint16_t *__restrict__ X, int64_t ld, const uint32_t *__restrict__ gcol, uint32_t g, uint32_t mult)
+{
+    const int64_t j = blockIdx.x;
+    const uint32_t m = gcol ? gcol[j] / g : mult;
+    if (m == 1u) return;
+    uint4 *cx = reinterpret_cast<uint4 *>(X + j * ld);
+    for (int64_t i = threadIdx.x; i < ld / 8; i += 256) {
+        const uint4 q = cx[i];
+        uint32_t w[4] = {q.x, q.y, q.z, q.w};
+        #pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t lo = w[k] & 0xFFFFu, hi = w[k] >> 16;
+            w[k] = (lo == 0xFFFFu ? lo : lo * m) | ((hi == 0xFFFFu ? hi : hi * m) << 16);
+        }
+        cx[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+void dosage_rescale(mih_mat *h, const uint32_t *gcol, uint32_t g, uint32_t mult)
+{
+    hipLaunchKernelGGL(k_dosage_scale, dim3((unsigned)h->p), dim3(256), 0, h->stream, h->Du, h->du_ld, gcol, g, mult);
 }
 
 }  // namespace mih
@@ -164,6 +190,19 @@ int mih_dosage_create_synthetic(int64_t n, int64_t p, uint64_t seed, int32_t den
     if ((rc = dosage_stats(h))) return fail(rc);
     *out = h;
     return MIH_OK;
+}
+
+int mih_dosage_regrid(mih_mat *h, int32_t denom)
+{
+    if (!h || !h->Du) { set_error("not a dosage handle"); return MIH_BAD_ARG; }
+    if (denom < 1 || denom > 32767 || denom % h->denom != 0) {
+        set_error("denom must be a multiple of the handle's denominator %d and at most 32767, got %d", h->denom, denom); return MIH_BAD_ARG;
+    }
+    if (denom == h->denom) return MIH_OK;
+    MIH_HIP(hipSetDevice(h->device));
+    dosage_rescale(h, nullptr, 1u, (uint32_t)(denom / h->denom));
+    h->denom = denom;
+    return dosage_stats(h);
 }
 
 int mih_dosage_export(const mih_mat *h, int64_t col0, int64_t ncols, uint16_t *out)

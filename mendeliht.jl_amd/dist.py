@@ -10,6 +10,7 @@ CPU-only test boxes).
    X'r pass itself needs no exchange.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -300,6 +301,49 @@ def column_block(p_global, rank, world):
     base, rem = divmod(p_global, world)
     lo = rank * base + min(rank, rem)
     return lo, base + (1 if rank < rem else 0)
+
+
+def read_bgen_shard(path, group=None, sample_path=None, threads=None, device=0):
+    """This rank's block of the variants of a BGEN file (column_block), streamed into the device (genotypes.read_bgen_device),
+    on the denominator every rank shares: one small all-gather of the ranks' denominators on the process group, then a regrid
+    to their lcm -- a divisor of 2^B - 1, so the single-process read's denominator.  Returns (x_shard, col_offset, p_global,
+    samples, chr, pos, ids, ref, alt), the metadata of this rank's variants.  A refusal on any rank is raised on every rank (the
+    lowest rank's: the first in file order); a common denominator above 32767 is an ArgumentError (a shard has no Float64
+    fallback)."""
+    import struct
+
+    import torch.distributed as dist
+
+    from .api import ArgumentError
+    from .genotypes import MAX_DENOM, read_bgen_device
+    on = dist.is_initialized()
+    rank = dist.get_rank(group) if on else 0
+    world = dist.get_world_size(group) if on else 1
+    with open(path, "rb") as f:
+        p_global = struct.unpack("<I", f.read(12)[8:12])[0]
+    col_offset, size = column_block(p_global, rank, world)
+    got, err = None, None
+    try:
+        got = read_bgen_device(path, sample_path, variants=range(col_offset, col_offset + size), threads=threads, device=device)
+    except Exception as e:      # noqa: BLE001  (reported to every rank before anyone raises: no rank is left in the all-gather)
+        err = e
+    mine = (0 if got is None else got[0].denom, None if err is None else f"{type(err).__name__}: {err}")
+    parts = [mine]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine, group=group)
+    failed = [e for _, e in parts if e is not None]
+    if failed:
+        if err is not None and failed[0] == mine[1]:
+            raise err
+        raise ArgumentError(failed[0])
+    den = 1
+    for d, _ in parts:
+        den = den * d // math.gcd(den, d)
+    if den > MAX_DENOM:
+        raise ArgumentError(f"{path}: the shards' common denominator {den} is above {MAX_DENOM}: a column-sharded fit needs one 16-bit grid")
+    x = got[0].regrid(den)
+    return (x, col_offset, p_global) + tuple(got[1:])
 
 
 def fit_iht_sharded(y, x_shard, z=None, *, col_offset, p_global, weight=None, native=False, ordered_sum=False, **kw):

@@ -168,7 +168,41 @@ def read_vcf(path, dosage=False):
 
 # ---- BGEN v1.2 ---------------------------------------------------------------------------------
 def _u(fmt, b, off):
+    if isinstance(b, _FileWindow):
+        return b.unpack(fmt, off)
     return struct.unpack_from(fmt, b, off)[0]
+
+
+class _FileWindow:
+    """A file read through a small window (os.pread) that answers what _u and _bgen_str ask of a bytes object: the header walk
+    reads each variant's header and at most WINDOW bytes beyond it, not the genotype block that follows (a mapping of the file
+    would fault in the pages around every header)."""
+
+    WINDOW = 1024
+
+    def __init__(self, f):
+        self.fd, self.size = f.fileno(), os.fstat(f.fileno()).st_size
+        self.lo, self.buf = 0, b""
+
+    def _cover(self, lo, hi):
+        if not (self.lo <= lo and hi <= self.lo + len(self.buf)):
+            self.lo, self.buf = lo, os.pread(self.fd, max(hi - lo, self.WINDOW), lo)
+        return lo - self.lo
+
+    def __len__(self):
+        return self.size
+
+    def __getitem__(self, sl):
+        lo, hi = max(sl.start, 0), min(sl.stop, self.size)
+        if hi <= lo:
+            return b""
+        o = self._cover(lo, hi)
+        return self.buf[o:o + hi - lo]
+
+    def unpack(self, fmt, off):
+        size = struct.calcsize(fmt)
+        o = self._cover(off, off + size)
+        return struct.unpack_from(fmt, self.buf, o)[0]
 
 
 def _bgen_str(b, off, width):
@@ -176,13 +210,9 @@ def _bgen_str(b, off, width):
     return b[off + width:off + width + n].decode(), off + width + n
 
 
-def read_bgen(path, sample_path=None):
-    """(columns of (numerators, denom), sample ids, chr, pos, ids, ref, alt) of a BGEN v1.2 file, layout 2, compression none
-    or zlib, unphased diploid biallelic: d = (2 k_BB + k_AB) / (2^B - 1), the ALT (second) allele counted as
-    second_dosage! does (wrapper.jl:381).  Sample ids from `sample_path` (default: the .sample file beside the .bgen), else
-    the file's own sample block, else 1..N."""
-    with open(path, "rb") as f:
-        b = f.read()
+def _bgen_head(b, path, sample_path):
+    """(offset of the first variant block, M, N, compression, sample ids) of a BGEN v1.2 file's header and sample block, with
+    read_bgen's checks and messages."""
     off, lh, m, n = _u("<I", b, 0), _u("<I", b, 4), _u("<I", b, 8), _u("<I", b, 12)
     if b[16:20] not in (b"bgen", b"\0\0\0\0"):
         raise ArgumentError(f"{path} is not a BGEN file")
@@ -211,19 +241,36 @@ def read_bgen(path, sample_path=None):
         samples = [str(i + 1) for i in range(n)]
     if len(samples) != n:
         raise DimensionMismatch(f"{path}: {len(samples)} sample ids for N = {n}")
+    return off, m, n, comp, samples
+
+
+def _bgen_variant(b, p_):
+    """The identifying data of the variant block at p_: (rsid, chr, pos, alleles, offset of its genotype block's length)."""
+    _vid, p_ = _bgen_str(b, p_, 2)
+    rsid, p_ = _bgen_str(b, p_, 2)
+    ch, p_ = _bgen_str(b, p_, 2)
+    vpos, k = _u("<I", b, p_), _u("<H", b, p_ + 4)
+    p_ += 6
+    alleles = []
+    for _ in range(k):
+        a, p_ = _bgen_str(b, p_, 4)
+        alleles.append(a)
+    return rsid, ch, vpos, alleles, p_
+
+
+def read_bgen(path, sample_path=None):
+    """(columns of (numerators, denom), sample ids, chr, pos, ids, ref, alt) of a BGEN v1.2 file, layout 2, compression none
+    or zlib, unphased diploid biallelic: d = (2 k_BB + k_AB) / (2^B - 1), the ALT (second) allele counted as
+    second_dosage! does (wrapper.jl:381).  Sample ids from `sample_path` (default: the .sample file beside the .bgen), else
+    the file's own sample block, else 1..N."""
+    with open(path, "rb") as f:
+        b = f.read()
+    off, m, n, comp, samples = _bgen_head(b, path, sample_path)
     cols, chrom, pos, ids, ref, alt = [], [], [], [], [], []
     p_ = off + 4
     for v in range(m):
-        _vid, p_ = _bgen_str(b, p_, 2)
-        rsid, p_ = _bgen_str(b, p_, 2)
-        ch, p_ = _bgen_str(b, p_, 2)
-        vpos, k = _u("<I", b, p_), _u("<H", b, p_ + 4)
-        p_ += 6
-        alleles = []
-        for _ in range(k):
-            a, p_ = _bgen_str(b, p_, 4)
-            alleles.append(a)
-        if k != 2:
+        rsid, ch, vpos, alleles, p_ = _bgen_variant(b, p_)
+        if len(alleles) != 2:
             raise ArgumentError(f"{path}: marker {v + 1} of BGEN is not biallelic!")
         clen = _u("<I", b, p_)
         blk = b[p_ + 4:p_ + 4 + clen]
@@ -258,6 +305,126 @@ def read_bgen(path, sample_path=None):
     return cols, samples, chrom, pos, ids, ref, alt
 
 
+class BgenIndex:
+    """What the variant headers of a BGEN file hold (bgen_index): samples, chrom, pos, ids, ref, alt of the variants walked,
+    `offsets` (int64) the file offset of each one's genotype block -- its 4-byte length field -- and the file's n (N),
+    nvariants (M) and compression."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _NotStreamable(ArgumentError):
+    """A BGEN file the streamed reader does not take: parse_genotypes reads it with read_bgen instead."""
+
+
+def _bgen_walk(path, sample_path=None, stop=None):
+    """The header walk of bgen_index over variants [0, stop) (all: None), skipping every genotype block by its stored length.
+    Also returns (v, ArgumentError) of the first variant that is not biallelic, or None: read_bgen's refusal of it comes after
+    the defects of the blocks before it.  A file too short for its headers raises _NotStreamable (read_bgen fails on it in
+    a way of its own)."""
+    try:
+        with open(path, "rb") as f:
+            b = _FileWindow(f)
+            off, m, n, comp, samples = _bgen_head(b, path, sample_path)
+            stop = m if stop is None else min(stop, m)
+            chrom, pos, ids, ref, alt = [], [], [], [], []
+            offsets = np.empty(stop, dtype=np.int64)
+            bad = None
+            p_ = off + 4
+            for v in range(stop):
+                rsid, ch, vpos, alleles, p_ = _bgen_variant(b, p_)
+                if len(alleles) != 2 and bad is None:
+                    bad = (v, ArgumentError(f"{path}: marker {v + 1} of BGEN is not biallelic!"))
+                offsets[v] = p_
+                p_ += 4 + _u("<I", b, p_)
+                if p_ > len(b):
+                    raise struct.error("genotype block past the end of the file")
+                chrom.append(ch); pos.append(vpos); ids.append(rsid)
+                ref.append(alleles[0] if alleles else ""); alt.append(alleles[1] if len(alleles) > 1 else "")
+    except (struct.error, ValueError, IndexError, UnicodeDecodeError) as e:
+        if isinstance(e, (ArgumentError, DimensionMismatch)):
+            raise
+        raise _NotStreamable(f"{path}: the BGEN headers cannot be walked ({e})") from None
+    return BgenIndex(samples=samples, chrom=chrom, pos=pos, ids=ids, ref=ref, alt=alt, offsets=offsets, n=n, nvariants=m,
+                     compression=comp), bad
+
+
+def bgen_index(path, sample_path=None, variants=None):
+    """Walk the headers of a BGEN v1.2 file without reading a genotype: sample ids by read_bgen's rules, per-variant chr, pos,
+    rsid, ref, alt, and the file offset of each genotype block (a BgenIndex), of every variant or of the contiguous range
+    `variants` of 0-based indices.  The header refusals are read_bgen's."""
+    if variants is not None and (not isinstance(variants, range) or variants.step != 1):
+        raise ArgumentError("variants must be a contiguous range of 0-based variant indices")
+    idx, bad = _bgen_walk(path, sample_path, None if variants is None else variants.stop)
+    if bad is not None:
+        raise bad[1]
+    if variants is not None:
+        a, e = variants.start, min(variants.stop, idx.nvariants)
+        for k in ("chrom", "pos", "ids", "ref", "alt", "offsets"):
+            setattr(idx, k, getattr(idx, k)[a:e])
+    return idx
+
+
+_BGEN_REFUSED = {1: "corrupt genotype block", 2: "genotype block disagrees with the header", 3: "ploidy other than 2 is not supported",
+                 4: "phased BGEN data is not supported", 6: "probabilities sum above 1"}
+_BGEN_CANNOT = {10: "more than 16 bits per probability", 11: "the bits per probability change between markers",
+                12: "16-bit probabilities on a grid finer than 1/32767", 13: "a genotype block read_bgen reads its own way"}
+
+
+def _bgen_nbits(path, offset, n, comp):
+    """The bit depth byte of the genotype block at `offset`."""
+    with open(path, "rb") as f:
+        f.seek(offset)
+        blk = f.read(_u("<I", f.read(4), 0))
+    if comp == 1:
+        blk = zlib.decompress(blk[4:])
+    return blk[9 + n]
+
+
+def read_bgen_device(path, sample_path=None, variants=None, threads=None, device=0):
+    """read_bgen's 7-tuple with a DosageMatrix in place of the columns, streamed from the file into the device: host threads
+    read and inflate the genotype blocks, the GPU unpacks them (mih_dosage_create_bgen).  The matrix is the one
+    DosageMatrix(*genotype_values(read_bgen(path)[0])) holds, bit for bit.  `variants`: a contiguous range of 0-based variant
+    indices (a column shard), the metadata of those variants returned.  Refusals are read_bgen's ArgumentErrors; a file this
+    path does not take (more than 16 bits per probability, bit depths that change, 16-bit fractional dosages) raises an
+    ArgumentError too -- parse_genotypes reads such files with read_bgen."""
+    import ctypes as C
+
+    from .api import _check, lib
+    path = str(path)
+    if variants is not None and (not isinstance(variants, range) or variants.step != 1):
+        raise ArgumentError("variants must be a contiguous range of 0-based variant indices")
+    idx, bad = _bgen_walk(path, sample_path, None if variants is None else variants.stop)
+    a, e = (0, idx.nvariants) if variants is None else (variants.start, variants.stop)
+    if not 0 <= a <= e <= idx.nvariants:
+        raise ArgumentError(f"variants {variants} out of range for {idx.nvariants} variants")
+    if idx.nvariants == 0:
+        raise _NotStreamable(f"{path} holds no variants")
+    if a == e:
+        raise ArgumentError(f"variants {variants} is empty")
+    stream_to = e if bad is None else min(e, bad[0])
+    if stream_to > a:
+        offs = np.ascontiguousarray(idx.offsets[a:stream_to])
+        h, den, bb, bw = C.c_void_p(None), C.c_int32(0), C.c_int64(-1), C.c_int32(0)
+        rc = lib().mih_dosage_create_bgen(os.fsencode(path), idx.n, stream_to - a, offs.ctypes.data_as(C.c_void_p), idx.compression,
+                                          int(threads or 0), device, C.byref(h), C.byref(den), C.byref(bb), C.byref(bw))
+        if rc != 0 and bw.value:
+            v, why = a + bb.value, bw.value
+            if why in _BGEN_CANNOT:
+                raise _NotStreamable(f"{path}: marker {v + 1}: {_BGEN_CANNOT[why]}: not streamed")
+            if why == 5:
+                raise ArgumentError(f"{path}: marker {v + 1}: {_bgen_nbits(path, int(idx.offsets[v]), idx.n, idx.compression)} bits per probability")
+            raise ArgumentError(f"{path}: marker {v + 1}: {_BGEN_REFUSED[why]}")
+        _check(rc)
+    if bad is not None and bad[0] < e:
+        if stream_to > a:
+            lib().mih_mat_destroy(h)
+        raise bad[1]
+    x = DosageMatrix(None, den.value, device=device, _handle=h)
+    return x, idx.samples, idx.chrom[a:e], idx.pos[a:e], idx.ids[a:e], idx.ref[a:e], idx.alt[a:e]
+
+
 # ---- parse_genotypes ---------------------------------------------------------------------------
 def parse_genotypes(tgtfile, dosage=False, device=0):
     """parse_genotypes(tgtfile, dosage) -- wrapper.jl:451-485: (X, sample_ids, chr, pos, snpid, ref, alt).  VCF (`.vcf`,
@@ -268,7 +435,10 @@ def parse_genotypes(tgtfile, dosage=False, device=0):
     if tgt.endswith((".vcf", ".vcf.gz")):
         cols, samples, chrom, pos, ids, ref, alt = read_vcf(tgt, dosage)
     elif tgt.endswith(".bgen"):
-        cols, samples, chrom, pos, ids, ref, alt = read_bgen(tgt)
+        try:
+            return read_bgen_device(tgt, device=device)
+        except _NotStreamable:          # read_bgen's own path: > 16 bits, mixed depths, 16-bit fractional dosages, its errors
+            cols, samples, chrom, pos, ids, ref, alt = read_bgen(tgt)
     elif all(os.path.isfile(tgt + e) for e in (".bed", ".bim", ".fam")):
         if dosage:
             raise ArgumentError("PLINK files detected but dosage = true!")
