@@ -163,3 +163,116 @@ def peel_rule(r, ratio=64.0, max_rows=64):
     rows = np.flatnonzero(a > tau)
     return rows if rows.size <= max_rows else np.zeros(0, dtype=np.int64)
 
+
+
+# ---- the 16-bit dosage matrix: the standardized matrix, an edge-case matrix, exact X'r and X beta, the counted error bounds ----
+def standardized(num, den, mu, sinv):
+    miss = num == 0xFFFF
+    return np.where(miss, 0.0, (num.astype(np.float64) / den - mu) * sinv)
+
+
+def edge_matrix(n, den, seed):
+    """Columns with mu near 0 and 2 (0-5), monomorphic at 0, 1 and 2 (6-8), all missing (9), monomorphic at 2 with sparse missing
+    entries (10), and ordinary fractional ones with 5 % missing (11-19).  Any n >= 1; the off-pole values go up to 2 den."""
+    rng = np.random.default_rng(seed)
+    cols = []
+    for _ in range(3):                                  # mu near 0 / near 2: one or two entries off the pole
+        c = np.zeros(n, np.int64); c[rng.choice(n, min(2, n), replace=False)] = rng.integers(1, 2 * den + 1, min(2, n)); cols.append(c)
+        c = np.full(n, 2 * den, np.int64); c[rng.choice(n, min(2, n), replace=False)] = rng.integers(0, 2 * den + 1, min(2, n)); cols.append(c)
+    cols += [np.zeros(n, np.int64), np.full(n, den, np.int64), np.full(n, 2 * den, np.int64), np.full(n, -1, np.int64)]
+    c = np.full(n, 2 * den, np.int64); c[::97] = -1; cols.append(c)                    # monomorphic at 2 with missing entries
+    for _ in range(9):
+        c = rng.integers(0, 2 * den + 1, n); c[rng.random(n) < 0.05] = -1; cols.append(c)
+    num = np.stack(cols, axis=1)
+    return np.where(num < 0, 0xFFFF, num).astype(np.uint16)
+
+
+def _dyadic(r):
+    """The doubles r_i as integers A_i over one power of two D: r_i = A_i / D exactly."""
+    ratios = [float(v).as_integer_ratio() for v in r]
+    D = max(q for _, q in ratios)
+    return np.array([a * (D // q) for a, q in ratios], dtype=object), D
+
+
+def exact_xtv(num, den, mu, sinv, r):
+    """sinv_j * sum_i (num_ij / den - mu_j) r_i over the non-missing i, exactly (mu_j, sinv_j the handle's own values)."""
+    from fractions import Fraction
+    A, D = _dyadic(r)
+    out = []
+    for j in range(num.shape[1]):
+        ok = num[:, j] != 0xFFFF
+        s_num = int(np.dot(num[ok, j].astype(object), A[ok])) if ok.any() else 0
+        s_r = int(A[ok].sum()) if ok.any() else 0
+        out.append(Fraction(float(sinv[j])) * (Fraction(s_num, den * D) - Fraction(float(mu[j])) * Fraction(s_r, D)))
+    return out
+
+
+def exact_xv(num, den, mu, sinv, idx, val):
+    """sum_t x_{i, idx[t]} val_t with x_ij = (num_ij / den - mu_j) sinv_j (0 where missing), exactly, for every row i."""
+    from fractions import Fraction
+    n = num.shape[0]
+    if len(idx) == 0:
+        return [Fraction(0)] * n
+    w = [Fraction(float(sinv[j])) * Fraction(float(v)) for j, v in zip(idx, val)]           # sinv_j val_t: dyadic rationals
+    m = [Fraction(float(mu[j])) * den for j in idx]                                         # mu_j den: the mean numerator
+    Dw = max(f.denominator for f in w); Dm = max(f.denominator for f in m)
+    a = np.array([int(f * Dw) for f in w], dtype=object)
+    b = np.array([int(f * Dm) for f in m], dtype=object)
+    sub = num[:, idx]
+    C = np.where(sub == 0xFFFF, 0, sub.astype(object) * Dm - b[None, :])                   # (num - mu den) Dm, 0 where missing
+    tot = C.dot(a)
+    return [Fraction(int(t), den * Dw * Dm) for t in tot]
+
+
+def dosage_host_stats(num, den):
+    """mun_j = fl(S / N) and sc_j = fl(sinv_j / den) as k_dosage_stats forms them (S, N exact integers in a double; every
+    operation a correctly rounded IEEE one on both sides), from the numerators alone."""
+    ok = num != 0xFFFF
+    S = np.where(ok, num, 0).astype(np.int64).sum(axis=0).astype(np.float64)
+    N = ok.sum(axis=0).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = np.where(N > 0, S / (N * float(den)), 0.0)
+        s = np.sqrt(m * (1.0 - m / 2.0))
+        sinv = np.where(s > 0, 1.0 / s, 1.0)
+        mun = np.where(N > 0, S / N, 0.0)
+    return mun, sinv / float(den), m, sinv
+
+
+def dosage_xtv_tol(num, den, R):
+    """The a-priori error bound of k_xtv_dosage_lds per column and residual (p x m), counted from its source; u = 2^-53,
+    steps = ceil(n / 1024), c_ij = num_ij - mun_j (0 where missing):
+
+        tol_j = 2u [ (4 steps + 12) sc_j sum_i |c_ij| |r_i|  +  2 sc_j mun_j sum_{i not missing} |r_i| ]
+
+    4 steps + 12: one rounding in num - mun; a row's product joins one of 4 chains per lane, and a chain takes 2 (loads u) x 2
+    (pairs hh) = 4 FMAs per 1024-row step; 2 additions join the 4 chains, 6 the 64 lanes (wave_sum), one multiply by sc, and
+    sc = fl(sinv / den) is one more rounding: 4 steps + 11 by the source, which the 4 steps + 12 this bound was set with covers.
+    The second term: the reference centres by the handle's mu_j = fl(S / (N den)), the kernel by mun_j = fl(S / N): two independent
+    roundings of the
+    same mean, each worth u mun_j on every non-missing row.  The leading 2 covers the second-order terms."""
+    n = num.shape[0]
+    mun, sc, _, _ = dosage_host_stats(num, den)
+    ok = num != 0xFFFF
+    c = np.where(ok, np.abs(num.astype(np.float64) - mun[None, :]), 0.0)
+    aR = np.abs(np.asarray(R, dtype=np.float64).reshape(n, -1))
+    steps = (n + 1023) // 1024
+    return 2.0 * 2.0 ** -53 * ((4 * steps + 12) * sc[:, None] * (c.T @ aR) + 2.0 * (sc * mun)[:, None] * (ok.astype(np.float64).T @ aR))
+
+
+def dosage_xv_tol(num, den, idx, val, groups=16):
+    """The a-priori error bound of k_xv_dosage + k_xv_reduce per row: an entry x_ij = fl(fl(num - mun_j) sc_j) carries three
+    roundings relative to |c_ij| sc_j (the subtraction, sc_j = fl(sinv_j / den), the product) and the two roundings of the mean
+    (2u mun_j sc_j, as in dosage_xtv_tol); a term passes at most per = ceil(nnz / G) FMAs of its group's chain and G additions of
+    the reduction, G = min(nnz, groups):
+
+        tol_i = 2u sum_t |val_t| sc_j [ (per + G + 3) |c_ij| + 2 mun_j ],   j = idx[t], over the non-missing (i, j)."""
+    nnz = len(idx)
+    if nnz == 0:
+        return np.zeros(num.shape[0])
+    G = min(nnz, groups); per = -(-nnz // G)
+    mun, sc, _, _ = dosage_host_stats(num, den)
+    sub = num[:, idx]
+    ok = sub != 0xFFFF
+    c = np.where(ok, np.abs(sub.astype(np.float64) - mun[idx][None, :]), 0.0)
+    w = np.abs(np.asarray(val, dtype=np.float64)) * sc[idx]
+    return 2.0 * 2.0 ** -53 * ((per + G + 3) * (c @ w) + 2.0 * (ok.astype(np.float64) @ (w * mun[idx])))

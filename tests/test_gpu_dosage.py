@@ -10,43 +10,10 @@ import numpy as np
 import pytest
 
 from conftest import FIX, GOLD, hash_folds
+from gpu_helpers import edge_matrix, exact_xtv, standardized
 from test_genotype_readers_cpu import bed_codes, write_bgen, write_vcf
 
 pytestmark = pytest.mark.gpu
-
-
-def standardized(num, den, mu, sinv):
-    miss = num == 0xFFFF
-    return np.where(miss, 0.0, (num.astype(np.float64) / den - mu) * sinv)
-
-
-def edge_matrix(n, den, seed):
-    """Columns with mu near 0 and 2, monomorphic at 0, 1 and 2, all missing, sparse missing, and ordinary fractional ones."""
-    rng = np.random.default_rng(seed)
-    cols = []
-    for _ in range(3):                                  # mu near 0 / near 2: one or two entries off the pole
-        c = np.zeros(n, np.int64); c[rng.choice(n, 2, replace=False)] = rng.integers(1, 2 * den, 2); cols.append(c)
-        c = np.full(n, 2 * den, np.int64); c[rng.choice(n, 2, replace=False)] = rng.integers(0, 2 * den, 2); cols.append(c)
-    cols += [np.zeros(n, np.int64), np.full(n, den, np.int64), np.full(n, 2 * den, np.int64), np.full(n, -1, np.int64)]
-    c = np.full(n, 2 * den, np.int64); c[::97] = -1; cols.append(c)                    # monomorphic at 2 with missing entries
-    for _ in range(9):
-        c = rng.integers(0, 2 * den + 1, n); c[rng.random(n) < 0.05] = -1; cols.append(c)
-    num = np.stack(cols, axis=1)
-    return np.where(num < 0, 0xFFFF, num).astype(np.uint16)
-
-
-def exact_xtv(num, den, mu, sinv, r):
-    """sinv_j * sum_i (num_ij / den - mu_j) r_i over the non-missing i, exactly (mu_j, sinv_j the handle's own values)."""
-    ratios = [v.as_integer_ratio() for v in r]
-    D = max(q for _, q in ratios)
-    A = np.array([a * (D // q) for a, q in ratios], dtype=object)         # r_i = A_i / D exactly
-    out = []
-    for j in range(num.shape[1]):
-        ok = num[:, j] != 0xFFFF
-        s_num = int(np.dot(num[ok, j].astype(object), A[ok])) if ok.any() else 0
-        s_r = int(A[ok].sum()) if ok.any() else 0
-        out.append(Fraction(sinv[j]) * (Fraction(s_num, den * D) - Fraction(mu[j]) * Fraction(s_r, D)))
-    return out
 
 
 def test_xtv_exact_bound_bits_and_fusion(mih):
