@@ -1,58 +1,13 @@
 // fit.hip -- fit_iht! (src/fit.jl:145-207) for ONE univariate fit and the step-by-step sessions: mih_fit_iht, mih_session_*,
-// mih_cv_meanloss, and the initialize_beta! regressions shared with the multivariate fit.  One IHTVariable, its kernels and its
-// steps (host-driven and resident on the device): fit_state.h; the lock-step drivers of cv_iht / iht_run_many_models:
-// fit_lockstep.hip.
+// mih_cv_meanloss.  One IHTVariable is declared in fit_state.h; its kernels and its steps (host-driven and resident on the device)
+// are in iht_var.hip; the lock-step drivers of cv_iht / iht_run_many_models: fit_lockstep.hip.
 //
 // What lives where: X (2-bit), y, z, cv_wts, xb, zc, mu, r, df and the projection buffer stay in HBM for the whole fit.  The model
 // is k-sparse: (index, value) lists -- in device memory while a fit steps resident (resident.inc), on the host otherwise.
 #include "fit_state.h"
-
-namespace mih {
-
-int init_beta_regress_device(const mih_mat *h, const double *w_dev, const double *Y_dev, int m, double N,
-                             const double *Sy_host, double *beta_dev, double *icpt_sum_host,
-                             DevBuf<double> &red, DevBuf<double> &scal, hipStream_t s, const XtvTune &tune)
-{
-    const int64_t n = h->n, p = h->p;
-    XtvWork xw; DevBuf<double> R, S, icpt, sxxd; DevBuf<uint32_t> M; DevBuf<int32_t> cnt;
-    MIH_TRY(xtv_work_init(h, xw, 1 + m, tune));
-    MIH_TRY(R.alloc((size_t)(1 + m) * n)); MIH_TRY(S.alloc((size_t)(1 + m) * p)); MIH_TRY(icpt.alloc(p));
-    hipLaunchKernelGGL(k_ib_rhs, dim3(nblk(n)), dim3(256), 0, s, Y_dev, w_dev, n, m, R.p);
-    MIH_TRY(xtv_device(h, xw, R.p, 1 + m, S.p, s));
-    if (h->kind == 0) {
-        int64_t nwords = h->n_pad / 16;
-        MIH_TRY(M.alloc(nwords)); MIH_TRY(cnt.alloc((size_t)2 * p));
-        MIH_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * 2 * p, s));
-        hipLaunchKernelGGL(k_ib_mask, dim3(nblk(nwords)), dim3(256), 0, s, w_dev, n, nwords, M.p);
-        dim3 grid((unsigned)((h->nbp + kIbBpPerBlock - 1) / kIbBpPerBlock), (unsigned)h->ncg);
-        hipLaunchKernelGGL(k_ib_counts, grid, dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X), h->nbp, p, M.p, cnt.p);
-    } else {
-        MIH_TRY(sxxd.alloc(p));
-        if (h->Du) hipLaunchKernelGGL(k_ib_dosage_sxx, dim3((unsigned)p), dim3(256), 0, s, dosage_view(h), w_dev, n, sxxd.p);
-        else if (h->Df) hipLaunchKernelGGL(k_ib_dense_sxx<float>, dim3((unsigned)p), dim3(256), 0, s, h->Df, w_dev, n, p, sxxd.p);
-        else hipLaunchKernelGGL(k_ib_dense_sxx<double>, dim3((unsigned)p), dim3(256), 0, s, h->D, w_dev, n, p, sxxd.p);
-    }
-    const int nsb = 64;
-    for (int t = 0; t < m; ++t) {
-        hipLaunchKernelGGL(k_ib_solve, dim3(nblk(p)), dim3(256), 0, s, S.p, S.p + (size_t)(1 + t) * p, cnt.p, h->miss_ptr, h->miss_row,
-                           w_dev, h->mu, h->sinv, h->kind, h->center, h->scale, h->impute, p, N, Sy_host[t], sxxd.p,
-                           beta_dev + (size_t)t * p, icpt.p);
-        hipLaunchKernelGGL(k_ib_sum, dim3(nsb), dim3(256), 0, s, icpt.p, p, red.p);
-        hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(256), 0, s, red.p, nsb, 1, scal.p);
-        MIH_HIP(hipMemcpyAsync(&icpt_sum_host[t], scal.p, sizeof(double), hipMemcpyDeviceToHost, s));
-        MIH_HIP(hipStreamSynchronize(s));
-    }
-    return MIH_OK;
-}
-
-static double sample_var(const double *a, int64_t n)
-{
-    double m = 0.0; for (int64_t i = 0; i < n; ++i) m += a[i]; m /= (double)n;
-    double s = 0.0; for (int64_t i = 0; i < n; ++i) s += (a[i] - m) * (a[i] - m);
-    return s / (double)(n - 1);
-}
-
-}  // namespace mih
+#include <chrono>
+#include <cstring>
+#include <limits>
 
 using namespace mih;
 
@@ -87,10 +42,6 @@ int mih_fit_iht(const mih_mat *h, const mih_fit_params *prm, const double *y, co
     return MIH_OK;
 }
 
-// ---- cv_iht: rolling lock-step -----------------------------------------------------------
-// The (fold, k) fits of cross_validation.jl:100-121 are independent; on one GPU they advance in
-
-
 struct mih_session_impl {
     IhtVar v;
     mih_fit_params prm;
@@ -121,7 +72,7 @@ static int session_steps(mih_session_impl *s, int64_t nsteps, double *logl, int6
 {
     IhtVar &v = s->v;
     int64_t total = 0;
-    IhtVar::ResRun rr;
+    ResRun rr;
     rr.issued = rr.done = s->steps; rr.limit = s->steps + nsteps; rr.max_step = s->prm.max_step;
     double sc = 0.0;
     for (int64_t t = 0; t < nsteps; ++t) {

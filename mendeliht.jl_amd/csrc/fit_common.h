@@ -1,5 +1,6 @@
-// fit_common.h -- small device helpers shared by the univariate (fit_state.h, fit.hip, fit_lockstep.hip) and multivariate
-// (mv.hip) IHT drivers.  Kernels are `static` so each translation unit gets its own copy.
+// fit_common.h -- small device helpers, the communicator of a column-sharded fit and the lanes' scheduler, shared by the univariate
+// (iht_var.hip, fit.hip, fit_lockstep.hip) and multivariate (mv.hip) IHT drivers and debias.hip.  Kernels are `static` so each
+// translation unit that launches them gets its own copy.
 #pragma once
 #include "common.h"
 #include <vector>
@@ -116,10 +117,75 @@ static __global__ void k_mask_to_wts(const uint8_t *__restrict__ m, int64_t n, i
 
 static inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// var(a) with the n - 1 divisor (pve.jl:22,32)
+static inline double sample_var(const double *a, int64_t n)
+{
+    double m = 0.0; for (int64_t i = 0; i < n; ++i) m += a[i]; m /= (double)n;
+    double s = 0.0; for (int64_t i = 0; i < n; ++i) s += (a[i] - m) * (a[i] - m);
+    return s / (double)(n - 1);
+}
+
 struct Sparse {                       // a k-sparse p-vector, sorted by index
     std::vector<int64_t> idx;
     std::vector<double> val;
     void clear() { idx.clear(); val.clear(); }
+};
+
+// The communicator of a column-sharded fit (mih_comm): this process owns columns [col0, col0 + p) of pg.  IhtVar and MvVar derive
+// from it.  With the measurement hook on every exchange is timed -- HIP events around a collective queued on the fit's stream, the
+// host clock around one the host waits for -- and kept per kind (mih_profile_exchange; the kinds: ExchRecord, common.h).
+struct ShardComm {
+    const mih_comm *comm = nullptr;
+    int64_t col0 = 0, pg = 0;
+    // comm = prm->comm (null: an unsharded fit over all p columns)
+    int validate(const mih_fit_params *prm, int64_t p)
+    {
+        comm = prm->comm; pg = p; col0 = 0;
+        if (!comm) return MIH_OK;
+        if (!comm->allreduce || !comm->allgather || comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world ||
+            comm->col_offset < 0 || comm->col_offset + p > comm->p_global) {
+            set_error("invalid mih_comm (callbacks, rank/world or column range)"); return MIH_BAD_ARG;
+        }
+        col0 = comm->col_offset; pg = comm->p_global;
+        return MIH_OK;
+    }
+    static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    static int fail(int rc) { set_error("communicator callback failed (%d)", rc); return MIH_BAD_ARG; }
+    // sum (op 0) or maximum (op 1) over the shards of a device vector: queued on stream s when the communicator is the library's
+    // own, else through the caller's callback (which is handed the device pointer) after a stream synchronisation
+    int allreduce_dev(const mih_mat *h, hipStream_t s, double *buf, int64_t cnt, int op, int kind) const
+    {
+        Profile &pf = *h->prof;
+        ExchRecord rec; rec.kind = kind;
+        const bool timed = pf.on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
+        if (timed) (void)hipEventRecord(rec.e0, s);
+        const int nrc = comm_native_allreduce_on_stream(comm, buf, cnt, op, s, h->device);
+        if (nrc >= 0) {
+            if (timed) { (void)hipEventRecord(rec.e1, s); std::lock_guard<std::mutex> g(pf.mu); pf.xopen.push_back(rec); }
+            return nrc;
+        }
+        if (timed) { (void)hipEventDestroy(rec.e0); (void)hipEventDestroy(rec.e1); }
+        const double t0 = now_ms();
+        MIH_HIP(hipStreamSynchronize(s));
+        int rc = comm->allreduce(comm->user, buf, cnt, op, 1);
+        pf.exch_host(kind, now_ms() - t0);
+        return rc ? fail(rc) : MIH_OK;
+    }
+    int allreduce_host(const mih_mat *h, double *buf, int64_t cnt, int op) const
+    {
+        const double t0 = now_ms();
+        int rc = comm->allreduce(comm->user, buf, cnt, op, 0);
+        h->prof->exch_host(3, now_ms() - t0);
+        return rc ? fail(rc) : MIH_OK;
+    }
+    int allgather_host(const mih_mat *h, const double *send, int64_t cnt, std::vector<double> &recv) const
+    {
+        recv.assign((size_t)cnt * comm->world, 0.0);
+        const double t0 = now_ms();
+        int rc = comm->allgather(comm->user, send, cnt, recv.data());
+        h->prof->exch_host(2, now_ms() - t0);
+        return rc ? fail(rc) : MIH_OK;
+    }
 };
 
 // ---- GLM closed forms (GLM.jl / Distributions.jl) --------------------

@@ -1,7 +1,17 @@
 // fit_lockstep.hip -- cv_iht and iht_run_many_models (src/cross_validation.jl:60-131, 232-273): the rolling lock-step drivers.  The
 // (fold, k) fits of a rank advance together, ONE fused X'R pass per round scores all of them; two lanes (host thread + stream +
-// workspace) pull fits from one queue.  Split out of fit.hip in round 6; one IHTVariable and its steps: fit_state.h.
+// workspace) pull fits from one queue.  Split out of fit.hip in round 6; one IHTVariable: fit_state.h (declared), iht_var.hip (its kernels and steps).
 #include "fit_state.h"
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <limits>
+#include <mutex>
+#include <string>
+#include <thread>
 
 using namespace mih;
 

@@ -294,7 +294,7 @@ static bool lu_logdet_inverse(const std::vector<double> &Ain, int r, double *log
 }
 
 // One mIHTVariable (src/data_structures.jl:140-180), device-resident.
-struct MvVar {
+struct MvVar : ShardComm {      // (comm, col0, pg and the exchanges of a column shard: fit_common.h)
     Arena arena;                                         // first member: outlives the buffers carved out of it (common.h)
     const mih_mat *h = nullptr;
     int64_t n = 0, p = 0, k = 0; int q = 0, r = 0;
@@ -364,42 +364,10 @@ struct MvVar {
     // n r + 1 doubles (X_S df_S of iht_stepsize!, the shards' |df_S|^2 riding as the last element), one of n r doubles per
     // update_xb!, and one all-gather of 1 + 2K doubles per projection -- the shards' top-K entries of vec(B) as (global linear
     // index, value) pairs, after which every rank holds the WHOLE k-sparse model of the step (Bg): _choose!'s count and rule and
-    // check_convergence's maxima are then computed locally and identically everywhere.
-    const mih_comm *comm = nullptr;
-    int64_t col0 = 0, pg = 0;
+    // check_convergence's maxima are then computed locally and identically everywhere.  The all-reduces are sums (op 0), timed as
+    // kind 0 with the step size's numerator riding along and as kind 1 for the plain products.
     Sparse Bg, B0g;                        // the whole model, global linear index i + r*(col0 + j); identical on every rank
     double spec_numer = 0.0;               // |df_S|^2 over all shards, home with the step-size denominator
-    static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    int comm_fail(int rc) { set_error("communicator callback failed (%d)", rc); return MIH_BAD_ARG; }
-    // sum over the shards of a device vector: queued on this stream when the communicator is the library's own, else through
-    // the caller's callback (which is handed the device pointer) after a stream synchronisation.  Timed by kind as in fit_state.h
-    // (0: with the step size's numerator riding along, 1: plain products)
-    int allreduce_dev(double *buf, int64_t cnt, int kind)
-    {
-        Profile &pf = *h->prof;
-        ExchRecord rec; rec.kind = kind;
-        const bool timed = pf.on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
-        if (timed) (void)hipEventRecord(rec.e0, s);
-        const int nrc = comm_native_allreduce_on_stream(comm, buf, cnt, 0, s, h->device);
-        if (nrc >= 0) {
-            if (timed) { (void)hipEventRecord(rec.e1, s); std::lock_guard<std::mutex> g(pf.mu); pf.xopen.push_back(rec); }
-            return nrc;
-        }
-        if (timed) { (void)hipEventDestroy(rec.e0); (void)hipEventDestroy(rec.e1); }
-        const double t0 = now_ms();
-        MIH_HIP(hipStreamSynchronize(s));
-        int rc = comm->allreduce(comm->user, buf, cnt, 0, 1);
-        pf.exch_host(kind, now_ms() - t0);
-        return rc ? comm_fail(rc) : MIH_OK;
-    }
-    int allgather_host(const double *send, int64_t cnt, std::vector<double> &recv)
-    {
-        recv.assign((size_t)cnt * comm->world, 0.0);
-        const double t0 = now_ms();
-        int rc = comm->allgather(comm->user, send, cnt, recv.data());
-        h->prof->exch_host(2, now_ms() - t0);
-        return rc ? comm_fail(rc) : MIH_OK;
-    }
 
     // shared_stream != null: one of a lock-step batch (mih_cv_mv): it runs on the batch's stream and leaves the
     // X'R pass to the batch driver
@@ -408,15 +376,10 @@ struct MvVar {
     {
         h = hh; n = h->n; p = h->p; r = (int)rr; q = (int)qq; k = prm->k; Y_host = Yh; Z_host = Zh; init_beta = prm->init_beta; tune = xtv_tune(prm);
         choose_cb = prm->comm ? nullptr : prm->choose; choose_user = prm->choose_user;
-        comm = prm->comm; pg = p; col0 = 0;
+        MIH_TRY(validate(prm, p));
         if (comm) {
-            if (!comm->allreduce || !comm->allgather || comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world ||
-                comm->col_offset < 0 || comm->col_offset + p > comm->p_global) {
-                set_error("invalid mih_comm (callbacks, rank/world or column range)"); return MIH_BAD_ARG;
-            }
             if (shared_stream) { set_error("cross-validation shards over (fold,k) combinations (rank/world), not over columns"); return MIH_BAD_ARG; }
             if (init_beta) { set_error("init_beta is not available for a column-sharded multivariate fit"); return MIH_BAD_ARG; }
-            col0 = comm->col_offset; pg = comm->p_global;
         }
         if (r < 1 || r > kMaxR) { set_error("number of traits r=%d must be in 1..%d", r, kMaxR); return MIH_BAD_DIM; }
         if (q < 1 || r * q > kMaxRQ) { set_error("r*q = %d exceeds %d", r * q, kMaxRQ); return MIH_BAD_DIM; }
@@ -490,7 +453,7 @@ struct MvVar {
         MIH_TRY(ensure_stage(nc));
         if (!nc) {
             MIH_HIP(hipMemsetAsync(BX.p, 0, sizeof(double) * (size_t)n * r, s));
-            return comm ? allreduce_dev(BX.p, n * r, 1) : MIH_OK;          // (a shard without a support column still joins the sum)
+            return comm ? allreduce_dev(h, s, BX.p, n * r, 0, 1) : MIH_OK;          // (a shard without a support column still joins the sum)
         }
         // coefficient matrix [trait][support column] (zero where a trait does not use the column), one upload, one launch
         xbcoef.assign((size_t)nc * r, 0.0);
@@ -503,7 +466,7 @@ struct MvVar {
         if ((size_t)nc * r > mcoef.n) { MIH_HIP(hipStreamSynchronize(s)); MIH_TRY(mcoef.alloc((size_t)nc * r * 2)); }
         MIH_TRY(upload_cols_coef(xbcoef));
         MIH_TRY(xv_sparse_multi_device(h, xv, sidx.p, mcoef.p, nc, r, BX.p, s, cols.data()));
-        return comm ? allreduce_dev(BX.p, n * r, 1) : MIH_OK;              // the shards' partial products
+        return comm ? allreduce_dev(h, s, BX.p, n * r, 0, 1) : MIH_OK;              // the shards' partial products
     }
     // update_mu! + update_resid! (+ Gram matrix resid*resid' for solve_Sigma!/loglikelihood)
     int resid_and_gram()
@@ -594,7 +557,7 @@ struct MvVar {
         return readback(scal.p, np_, df2.data());   // [i + r*l]
     }
     // The end of a step (or of the initialisation) and the beginning of the next step in ONE host synchronisation (the univariate
-    // step_post_fused, fit_state.h): [with_df2: df2 = T1 Z' (score!, multivariate.jl:88-91)], df on the support (gathered on the
+    // step_post_fused, iht_var.hip): [with_df2: df2 = T1 Z' (score!, multivariate.jl:88-91)], df on the support (gathered on the
     // device, [trait][column]) and the whole iht_stepsize! of the next step -- X_S df_S straight from the device copy of df_S,
     // the pivoted Cholesky factor of Gamma, the weighted sum of squares -- are queued back to back and come home in one copy:
     // [df_S | df2 | sum].  Two synchronisations and three small copies less per iteration than three separate round trips; the
@@ -630,7 +593,7 @@ struct MvVar {
         } else MIH_HIP(hipMemsetAsync(T1.p, 0, sizeof(double) * (size_t)n * r, s));
         if (comm) {
             hipLaunchKernelGGL(k_mv_sumsq, dim3(1), dim3(256), 0, s, gval.p, (int64_t)ncr, T1.p + (size_t)n * r);
-            MIH_TRY(allreduce_dev(T1.p, n * r + 1, 0));
+            MIH_TRY(allreduce_dev(h, s, T1.p, n * r + 1, 0, 0));
             hipLaunchKernelGGL(k_mv_copy1, dim3(1), dim3(1), 0, s, T1.p + (size_t)n * r, d_sum + 1);
         }
         launch_mv_apply((unsigned)nb, s, T1.p, n, r, rmat(spec_U), 1, w.p, (double *)nullptr, red.p);
@@ -679,7 +642,7 @@ struct MvVar {
         } else MIH_HIP(hipMemsetAsync(T1.p, 0, sizeof(double) * (size_t)n * r, s));
         if (comm) {
             hipLaunchKernelGGL(k_mv_sumsq, dim3(1), dim3(256), 0, s, mcoef.p, nc * r, T1.p + (size_t)n * r);
-            MIH_TRY(allreduce_dev(T1.p, n * r + 1, 0));
+            MIH_TRY(allreduce_dev(h, s, T1.p, n * r + 1, 0, 0));
             hipLaunchKernelGGL(k_mv_copy1, dim3(1), dim3(1), 0, s, T1.p + (size_t)n * r, scal.p + 1);
         }
         pivoted_chol_triu(G, r);                                   // Gamma is left holding U (fit.jl:230-232 recomputes it)
@@ -781,7 +744,7 @@ struct MvVar {
         }
         return MIH_OK;
     }
-    // project_k!(v) over the shards (IhtVar::project_full_sharded of fit_state.h for vec(B)): the K-th largest |entry| of the whole
+    // project_k!(v) over the shards (IhtVar::project_full_sharded of iht_var.hip for vec(B)): the K-th largest |entry| of the whole
     // r(pg + q) vector is the K-th largest of the union of every shard's own top-K and the covariate tail (which every rank
     // holds); ties at that value are kept.  A shard sends its candidates as (global linear index, value) pairs, so every rank ends
     // up with the whole model of the step (Bg).  A shard with more than K entries at or above its own threshold (exact ties
@@ -808,7 +771,7 @@ struct MvVar {
         std::vector<double> mine((size_t)slot, -1.0), all;        // index -1 = no entry
         mine[0] = (double)sv.size();
         for (int64_t t = 0; t < K && t < (int64_t)ord.size(); ++t) { mine[1 + 2 * t] = (double)(col0 * r + si[ord[(size_t)t]]); mine[2 + 2 * t] = sv[ord[(size_t)t]]; }
-        MIH_TRY(allgather_host(mine.data(), slot, all));
+        MIH_TRY(allgather_host(h, mine.data(), slot, all));
         std::vector<double> mags;
         for (int32_t rk = 0; rk < comm->world; ++rk)
             for (int64_t t = 0; t < K; ++t) { const double *e = &all[(size_t)rk * slot + 1 + 2 * t]; if (e[0] >= 0.0) mags.push_back(std::fabs(e[1])); }
@@ -1074,13 +1037,6 @@ static int mv_check(const mih_mat *h, const mih_fit_params *prm)
     if (!(prm->tol > 2.220446049250313e-16)) { set_error("Value of global tol must exceed machine precision!"); return MIH_BAD_ARG; }
     if (h->kind == 0 && !h->center) { set_error("x is not centered! Please construct SnpLinAlg{Float64}(::SnpArray, center=true, scale=true)"); return MIH_NOT_CENTERED; }
     return MIH_OK;
-}
-
-static double sample_var(const double *a, int64_t n)
-{
-    double m = 0.0; for (int64_t i = 0; i < n; ++i) m += a[i]; m /= (double)n;
-    double s = 0.0; for (int64_t i = 0; i < n; ++i) s += (a[i] - m) * (a[i] - m);
-    return s / (double)(n - 1);
 }
 
 }  // namespace mih

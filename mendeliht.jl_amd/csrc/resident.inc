@@ -1,4 +1,5 @@
-// resident.inc -- iht_one_step! (src/fit.jl:213-263) resident on the device.  Included by fit_state.h inside namespace mih.
+// resident.inc -- iht_one_step! (src/fit.jl:213-263) resident on the device.  Included by iht_var.hip inside namespace mih; the control
+// block, the step record and the argument structs of its kernels (ResCtl, ResRecord, ResPtrs, ResMat) are declared in fit_state.h.
 //
 // The host-driven step of rounds 1-4 kept the k-sparse model (b, b0, best_b) as host lists, finished project_k! on the host and
 // took the backtracking decision there: 26 launches and three host waits between two X'r passes.  Here the iterate, the top-k
@@ -41,56 +42,11 @@
 
 constexpr int kResRing = 8;               // step records in pinned host memory
 constexpr int kResShardList = 1024;        // longest list the sharded select handles (its pool of candidates: kResMaxInBin)
-constexpr int kResMaxAttempts = 8;        // attempts of a step the direct gather keeps a forecast for (later ones: histograms)
 constexpr int kResMaxList = 2048;         // longest survivor list k_res_select sorts in LDS
 constexpr int kResBigList = 8192;         // ... and k_res_select<BIG> in a scratch block of device memory (round 6: models beyond ~2000 effects stay resident)
 constexpr int kResBigScratchWords = 8 * kResBigList;      // 64-bit words of that block: s_idx, s_val, o_idx, o_val, t_idx, t_val, {fresh_t, o_slot}, {rank_of, -}
 constexpr int kResMaxInBin = 2048;        // entries it ranks among themselves (those sharing the threshold's 22-bit prefix; all candidates of a direct gather)
 enum { RES_ACCEPT = 0, RES_PENDING = 1, RES_STOP_CONVERGED = 2, RES_STOP_NAN = 3, RES_STOP_INF = 4, RES_ABORT = 5, RES_REDO_SLOW = 6 };
-
-struct ResModel { int64_t cnt; uint64_t idc; double c[kMaxQ]; };
-struct ResCtl {
-    int32_t live_epoch;       // kernels launched with another epoch do nothing
-    int32_t cur;              // model buffer of the current iterate (b at the start of a step, b0 while it runs); 1 - cur: candidate
-    int32_t es;               // backtracks of the running step so far
-    int32_t iter;             // steps completed (fit.jl's iteration counter)
-    int32_t arm_stop, min_iter, max_step, pad0;
-    int32_t nfresh[2];        // per model buffer: entries whose column is not in the cache yet
-    uint32_t ctr[6];          // last-block counters (left at zero)
-    double eta;               // step size of the running step before any halving
-    double logl_cur, best_logl, tol, tol_stop;
-    double df2[kMaxQ];        // Z'r of the last score
-    uint64_t topk[4];         // two-pass select: exponent bin, remaining rank, lower-bound key, 22-bit prefix
-    uint64_t thr_key[kResMaxAttempts];   // |K-th largest| of the last projection made as attempt a of a step, as a key (0: unknown), and
-    double thr_eta[kResMaxAttempts];     // the step size it was made with: the direct gather's forecast for the next attempt a
-    ResModel m[2], best;
-    // column-sharded fit: the WHOLE model of each iterate as (global index, value) lists (check_convergence and _choose!'s count are
-    // global), the shard's own candidates of the running projection
-    int64_t gcnt[2], lc_cnt;
-};
-struct ResRecord { double logl, tol, eta; int32_t status, nbt, iter, cur; int64_t support; uint64_t seq; };      // seq is stored last
-struct ResPtrs {
-    ResCtl *ctl;
-    int64_t *idx[3]; double *val[3];          // [0], [1]: the two iterates; [2]: the best model
-    int32_t *slot[2], *fresh[2];              // cache slot of every entry; positions of the entries still to be copied in
-    double *gval, *coefA, *coefB;             // df on the support; k_xv_coef's coefficients of the list about to be multiplied
-    uint32_t *hist;                           // 2 x 2048 bins
-    uint64_t *sel; uint32_t sel_cap;          // candidates of the select: sel[0] = count, pairs behind sel[2]
-    int64_t kcap;                             // entries the lists hold
-    ResRecord *rec;                           // pinned ring
-    uint64_t *big;                            // k_res_select<BIG>'s scratch (kResBigScratchWords), or null
-    // column-sharded fit (null / 0 otherwise)
-    int64_t *gidx[2]; double *gvals[2];       // the whole model of the two iterates, global indices
-    int64_t *lc_idx; double *lc_val;          // this shard's survivors of its own top-K (k_res_select_local)
-    double *msg, *msgs;                       // this shard's message of the projection's all-gather, and everybody's
-    int32_t world, rank; int64_t col0;
-};
-struct ResMat {                               // what the kernels need of the 2-bit matrix and its column cache
-    const uint32_t *X; int64_t nbp, ndw, n, p;
-    uint32_t *cache; int32_t slots;
-    const double *mu, *sinv; int center, scale;
-    const int64_t *miss_ptr; const int32_t *miss_row;
-};
 
 // The gate word: 2 * epoch + phase.  Phase 0 (between two attempts series): the kernels that end a step (residual, statistics, the
 // X'r pass) and those that begin the next (X_S df_S, the step size) run; phase 1: the kernels of an attempt run -- whichever
@@ -1405,7 +1361,6 @@ k_res_decide(ResPtrs P, int epoch, int attempt, int next_attempt_queued, uint64_
 // (b, t) of k_r_stats visits rows 256 b + t + 16384 k; its even visits are walker (b, t) of k_zt_r, its odd ones walker (b + 64, t).
 // The second stage of both (64 and 128 partials) is left to the kernels behind: k_digits' blocks redo the statistics' for
 // themselves, its block 0 also Z'r.
-constexpr int kStatBlocksRes = 64;            // = kStatBlocks of xtv.hip
 // block_sum's tree over the 256 walkers of one block, by ONE wave that holds walker l, l + 64, l + 128, l + 192 in lane l: the same
 // pairs in the same order (red[t] += red[t + s] for s = 128, 64, ..., 1), the result in lane 0
 __device__ __forceinline__ double res_tree256_sum(double v0, double v1, double v2, double v3)
@@ -1429,8 +1384,8 @@ __device__ __forceinline__ double res_tree256_max(double v0, double v1, double v
 // here, where nothing but these sums is written (12 us for the whole kernel).  A workgroup-scope fence is NOT enough: it compiles
 // to nothing for global stores, the ticket overtook the sums now and then, and a stale partial of the step before gave Z'r a
 // relative error of 1e-6 (caught by test_large_k_and_many_covariates in one run of three).
-// grid (4 * kStatBlocksRes, ceil(q / 4)) x 64 threads: slice y takes covariates 4y .. 4y + 3 (slice 0 also the statistics).
-// walk: [slices][kStatBlocksRes][10][256] doubles (sum, max, 2 x 4 covariate sums), tick: [slices][kStatBlocksRes] zeros.
+// grid (4 * kStatBlocks, ceil(q / 4)) x 64 threads: slice y takes covariates 4y .. 4y + 3 (slice 0 also the statistics).
+// walk: [slices][kStatBlocks][10][256] doubles (sum, max, 2 x 4 covariate sums), tick: [slices][kStatBlocks] zeros.
 constexpr int kResStatCov = 4;
 static __global__ void __launch_bounds__(64)
 k_res_stats(ResPtrs P, int epoch, const double *__restrict__ z, const double *__restrict__ r, int64_t n, int q,
@@ -1441,7 +1396,7 @@ k_res_stats(ResPtrs P, int epoch, const double *__restrict__ z, const double *__
     const int slice = blockIdx.y, blk = blockIdx.x >> 2, t = (blockIdx.x & 3) * 64 + threadIdx.x;      // walker t of walk-block blk
     const int l0 = slice * kResStatCov, nl = q - l0 < kResStatCov ? q - l0 : kResStatCov;
     const bool stats = slice == 0;
-    const int64_t stride = 256ll * kStatBlocksRes;
+    const int64_t stride = 256ll * kStatBlocks;
     double mx = 0.0, sm = 0.0, za[2][kResStatCov];
     #pragma unroll
     for (int c = 0; c < kResStatCov; ++c) { za[0][c] = 0.0; za[1][c] = 0.0; }
@@ -1463,7 +1418,7 @@ k_res_stats(ResPtrs P, int epoch, const double *__restrict__ z, const double *__
             for (int c = 0; c < kResStatCov; ++c) za[u & 1][c] += zv[c][u] * rv[u];      // (sixteen visits per round: the parity of u is the parity of the visit)
         }
     }
-    double *mine = walk + ((size_t)slice * kStatBlocksRes + blk) * 10 * 256;
+    double *mine = walk + ((size_t)slice * kStatBlocks + blk) * 10 * 256;
     __hip_atomic_store(&mine[t], sm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&mine[256 + t], mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     #pragma unroll
@@ -1473,7 +1428,7 @@ k_res_stats(ResPtrs P, int epoch, const double *__restrict__ z, const double *__
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     unsigned ticket = 0;
-    if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(&tick[(size_t)slice * kStatBlocksRes + blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(&tick[(size_t)slice * kStatBlocks + blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     ticket = __shfl(ticket, 0, 64);
     if (ticket != 3u) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -1491,9 +1446,9 @@ k_res_stats(ResPtrs P, int epoch, const double *__restrict__ z, const double *__
     for (int c = 0; c < nl; ++c) {
         four(2 + c, v4); const double even = res_tree256_sum(v4[0], v4[1], v4[2], v4[3]);
         four(6 + c, v4); const double odd = res_tree256_sum(v4[0], v4[1], v4[2], v4[3]);
-        if (l == 0) { zpart[(int64_t)(l0 + c) * kZtrBlocks + blk] = even; zpart[(int64_t)(l0 + c) * kZtrBlocks + blk + kStatBlocksRes] = odd; }
+        if (l == 0) { zpart[(int64_t)(l0 + c) * kZtrBlocks + blk] = even; zpart[(int64_t)(l0 + c) * kZtrBlocks + blk + kStatBlocks] = odd; }
     }
-    if (l == 0) tick[(size_t)slice * kStatBlocksRes + blk] = 0;
+    if (l == 0) tick[(size_t)slice * kStatBlocks + blk] = 0;
 }
 
 // (round 6) The outlier side channel of the fixed-point residual (peel.h) in the resident chain: ONE workgroup between k_res_stats and
@@ -1506,5 +1461,5 @@ k_res_peel(ResPtrs P, int epoch, const double *__restrict__ r, int64_t n, const 
 {
     if (res_dead(P.ctl, epoch, -1)) return;
     const int64_t nb64 = (n + 255) / 256;
-    (void)peel_decide(r, n, spart, (int)(nb64 < kStatBlocksRes ? nb64 : kStatBlocksRes), pl);
+    (void)peel_decide(r, n, spart, (int)(nb64 < kStatBlocks ? nb64 : kStatBlocks), pl);
 }

@@ -1530,7 +1530,6 @@ static void launch_dosage_lds(const mih_mat *h, const double *r_dev, int m, doub
 }
 
 constexpr int kMaxSplits = 16;
-constexpr int kStatBlocks = 64;
 
 // mih_fit_params::xtv_digits / the digits argument of mih_xtv_batched_fmt (ids = base * 100 + digits, include/mendeliht_hip.h)
 static bool digit_mode(int id, DigitMode &dm)

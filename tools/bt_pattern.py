@@ -1,5 +1,5 @@
 """The backtrack count of every step of the bench's fit (configs[2], bench.py's data), one iht_one_step! per call.
-usage: python tools/bt_pattern.py [steps]   -- what the attempt-slot forecast of the resident chain (fit.hip: res_spec) has to predict"""
+usage: python tools/bt_pattern.py [steps]   -- what the attempt-slot forecast of the resident chain (iht_var.hip: res_spec) has to predict"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
