@@ -2,7 +2,9 @@
  * mendeliht_hip_probes.h -- extra entry points of the MEASUREMENT build (libmendeliht_hip_probes.so = the product's
  * sources compiled with -DMIH_PROBES).  Not part of the drop-in boundary and not exported by libmendeliht_hip.so:
  * tools/ and the "this switch changes nothing" tests use them to sweep launch shapes, to cross-check the product's
- * kernels bit for bit against the round-1 kernel families, and to run timing probes.  The measurement build also reads
+ * kernels bit for bit against the round-1 kernel families, to run timing probes, and to drive sequences of calls on ONE
+ * workspace (mih_probe_xtv_sequence: fused X'r passes; mih_probe_xv_sequence: the cached and multi-trait X beta paths of a
+ * fit).  The measurement build also reads
  * the MENDELIHT_* A/B environment switches (XTV_MAX_OPS, XTV_SLICES, XTV_NO_HALF, CV_LANES, CV_NO_MERGE,
  * CV_NO_INIT_SHARE, CV_NO_COOP, COOP_SPIN_US, CV_TRACE, INGEST_TRACE, INGEST_THREADS, TRACE_ETA, NO_SPIN, NO_ARENA, NO_RESERVE,
  * NO_RESIDENT, TOPK_RADIX8, XV_MULTI, RES_FORCE_ABORT_ES, DEBIAS_TRACE = the IRLS iterates of debias!'s GLM refit on stderr); the
@@ -29,6 +31,18 @@ int mih_probe_set_max_fused(int max_nr);
  * (p * ms[0] doubles, then p * ms[1], ...).  For the test that a pass ignores what an earlier pass with another residual
  * count left in the unused digit columns of its last operand (flat packing, csrc/xtv.hip). */
 int mih_probe_xtv_sequence(const mih_mat *h, const double *R, int mcap, const int *ms, int nms, int digits, double *OUT);
+/* X beta over a small support, ncalls products one after the other on ONE workspace (xv_work_init(h, w, max_nnz, cache_nnz):
+ * its LRU column cache, its coefficient buffers) with ONE pinned upload ring sized as a fit sizes it -- the paths a fit takes
+ * from step to step, which mih_xv_sparse (fresh workspace, direct kernel) never does.  Call c has nnz[c] column indices and
+ * m[c] * nnz[c] coefficients (trait-major), concatenated over the calls in idx_cat / val_cat.  m[c] == 1: the single-vector
+ * product with the host's copy of the indices (column cache; the direct kernel when the support outgrows it); flags[c] bit 0:
+ * slot and fill lists through the pinned ring, bit 1: the coefficients are gathered from a length-p vector the entry
+ * scatters them into (later duplicates of an index win) and also returned in GATHERED at the call's place in val_cat's
+ * layout, bit 2: clamp to [-20, 20].  m[c] > 1 (flags[c] must be 0): the multi-trait product (MENDELIHT_XV_MULTI selects its
+ * kernel).  OUT: the results back to back, m[c] * n doubles per call.  GATHERED may be null when no call gathers.  The stream
+ * is not synchronised between the calls. */
+int mih_probe_xv_sequence(const mih_mat *h, int64_t max_nnz, int64_t cache_nnz, int ncalls, const int64_t *nnz, const int *m,
+                          const int *flags, const int64_t *idx_cat, const double *val_cat, double *OUT, double *GATHERED);
 #ifdef __cplusplus
 }
 #endif

@@ -643,3 +643,61 @@ extern "C" int mih_xv_sparse(const mih_mat *h, const int64_t *idx, const double 
     MIH_HIP(hipStreamSynchronize(h->stream));
     return MIH_OK;
 }
+
+#ifdef MIH_PROBES
+// include/mendeliht_hip_probes.h: a sequence of X beta products on ONE workspace with its column cache and ONE pinned ring (what a
+// fit does from step to step).  The calls are queued back to back -- nothing synchronises the stream between them but the
+// workspace's own regrowth and the ring's own wrap -- and the results come home in one copy at the end.
+extern "C" int mih_probe_xv_sequence(const mih_mat *h, int64_t max_nnz, int64_t cache_nnz, int ncalls, const int64_t *nnz, const int *m,
+                                     const int *flags, const int64_t *idx_cat, const double *val_cat, double *OUT, double *GATHERED)
+{
+    if (!h || !nnz || !m || !flags || !OUT || ncalls < 1 || max_nnz < 0) { set_error("null/invalid argument"); return MIH_BAD_ARG; }
+    size_t tot_idx = 0, tot_val = 0, tot_out = 0;
+    bool gathers = false;
+    for (int c = 0; c < ncalls; ++c) {
+        if (nnz[c] < 0 || m[c] < 1) { set_error("call %d: nnz = %lld, m = %d", c, (long long)nnz[c], m[c]); return MIH_BAD_ARG; }
+        if (flags[c] < 0 || flags[c] > 7 || (m[c] > 1 && flags[c] != 0)) { set_error("call %d: flags = %d with m = %d", c, flags[c], m[c]); return MIH_BAD_ARG; }
+        if (nnz[c] > 0 && (!idx_cat || !val_cat)) { set_error("null/invalid argument"); return MIH_BAD_ARG; }
+        for (int64_t t = 0; t < nnz[c]; ++t) {
+            const int64_t j = idx_cat[tot_idx + (size_t)t];
+            if (j < 0 || j >= h->p) { set_error("call %d: column index %lld out of range", c, (long long)j); return MIH_BAD_DIM; }
+        }
+        gathers |= (flags[c] & 2) != 0;
+        tot_idx += (size_t)nnz[c]; tot_val += (size_t)nnz[c] * m[c]; tot_out += (size_t)h->n * m[c];
+    }
+    if (gathers && !GATHERED) { set_error("flags ask for the gathered coefficients but GATHERED is null"); return MIH_BAD_ARG; }
+    MIH_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    XvWork w;
+    MIH_TRY(xv_work_init(h, w, max_nnz, cache_nnz));
+    HostStage stage;
+    MIH_TRY(stage.init(2 * (size_t)std::max<int64_t>(max_nnz, 64) + 8));          // IhtVar::init: 2 kcap + 8 words per slot
+    DevBuf<int64_t> di; DevBuf<double> dv, dout, gsrc, gout;
+    MIH_TRY(di.alloc(tot_idx)); MIH_TRY(dv.alloc(tot_val)); MIH_TRY(dout.alloc(tot_out));
+    MIH_TRY(gsrc.alloc(gathers ? (size_t)h->p : 1)); MIH_TRY(gout.alloc(gathers ? tot_val : 1));
+    if (tot_idx) MIH_HIP(hipMemcpyAsync(di.p, idx_cat, sizeof(int64_t) * tot_idx, hipMemcpyHostToDevice, s));
+    if (tot_val) MIH_HIP(hipMemcpyAsync(dv.p, val_cat, sizeof(double) * tot_val, hipMemcpyHostToDevice, s));
+    if (gathers) MIH_HIP(hipMemsetAsync(gout.p, 0, sizeof(double) * std::max<size_t>(tot_val, 1), s));
+    std::vector<std::vector<double>> dense;           // the length-p vectors of the gathering calls (alive until the final synchronisation)
+    size_t io = 0, vo = 0, oo = 0;
+    for (int c = 0; c < ncalls; ++c) {
+        const int64_t k = nnz[c];
+        if (m[c] > 1)
+            MIH_TRY(xv_sparse_multi_device(h, w, di.p + io, dv.p + vo, k, m[c], dout.p + oo, s, idx_cat + io));
+        else if (flags[c] & 2) {
+            dense.emplace_back((size_t)h->p, 0.0);
+            for (int64_t t = 0; t < k; ++t) dense.back()[(size_t)idx_cat[io + (size_t)t]] = val_cat[vo + (size_t)t];
+            MIH_HIP(hipMemcpyAsync(gsrc.p, dense.back().data(), sizeof(double) * (size_t)h->p, hipMemcpyHostToDevice, s));
+            MIH_TRY(xv_sparse_device(h, w, di.p + io, nullptr, k, dout.p + oo, (flags[c] & 4) != 0, s, idx_cat + io,
+                                     (flags[c] & 1) ? &stage : nullptr, gsrc.p, gout.p + vo));
+        } else
+            MIH_TRY(xv_sparse_device(h, w, di.p + io, dv.p + vo, k, dout.p + oo, (flags[c] & 4) != 0, s, idx_cat + io,
+                                     (flags[c] & 1) ? &stage : nullptr));
+        io += (size_t)k; vo += (size_t)k * m[c]; oo += (size_t)h->n * m[c];
+    }
+    MIH_HIP(hipMemcpyAsync(OUT, dout.p, sizeof(double) * tot_out, hipMemcpyDeviceToHost, s));
+    if (gathers && tot_val) MIH_HIP(hipMemcpyAsync(GATHERED, gout.p, sizeof(double) * tot_val, hipMemcpyDeviceToHost, s));
+    MIH_HIP(hipStreamSynchronize(s));
+    return MIH_OK;
+}
+#endif

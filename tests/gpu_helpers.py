@@ -164,6 +164,91 @@ def peel_rule(r, ratio=64.0, max_rows=64):
     return rows if rows.size <= max_rows else np.zeros(0, dtype=np.int64)
 
 
+def xv_documented_order(G, a, b, max_groups=16):
+    """The summation order csrc/xv.hip documents for X beta over a support of the 2-bit matrix, restated: G (n x nnz) the stored
+    dosages 0 / 1 / 2 of the support columns in LIST order (a missing entry is stored as 0), a_t = sinv_t v_t (or v_t) and
+    b_t = -mu_t a_t (or 0.0) as doubles.  groups = min(nnz, 16), per = ceil(nnz / groups); group g covers the columns
+    [g per, min((g + 1) per, nnz)); acc and bsum accumulate in column order, part_g = acc + bsum, out = ((0.0 + part_0) +
+    part_1) + ... over all `groups` (an empty trailing group adds acc = bsum = +0.0).  g a is exact in f64 for g in {0, 1, 2}, so
+    fma(g, a, acc) is acc + g * a with ONE rounding and numpy predicts the kernel's bits.  The fix-up of imputed entries is not
+    part of it."""
+    G = np.asarray(G)
+    n, nnz = G.shape
+    out = np.zeros(n)
+    if nnz == 0:
+        return out
+    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
+    groups = min(nnz, max_groups); per = -(-nnz // groups)
+    for g in range(groups):
+        acc = np.zeros(n); bsum = np.float64(0.0)
+        for t in range(g * per, min((g + 1) * per, nnz)):
+            acc = acc + G[:, t].astype(np.float64) * a[t]
+            bsum = bsum + b[t]
+        out = out + (acc + bsum)
+    return out
+
+
+def _signed_limbs(vals, bits=26):
+    """Python integers as rows of signed `bits`-bit limbs (int64): v = sum_l limb[l] 2^(bits l)."""
+    L = max(1, max((abs(v).bit_length() for v in vals), default=1) // bits + 1)
+    out = np.zeros((len(vals), L), dtype=np.int64)
+    mask = (1 << bits) - 1
+    for t, v in enumerate(vals):
+        s, w = (-1 if v < 0 else 1), abs(v)
+        for l in range(L):
+            out[t, l] = s * ((w >> (bits * l)) & mask)
+    return out
+
+
+def _int_matvec(M, vals, bits=26):
+    """M (rows x k, small non-negative integers) times the Python integers vals, exactly: a list of Python integers per row.  The
+    limb columns go through an int64 matrix product (|entries| <= 2 k 2^26), the limbs are joined in Python integers."""
+    limbs = _signed_limbs(vals, bits)
+    part = np.asarray(M, dtype=np.int64) @ limbs
+    acc = np.zeros(part.shape[0], dtype=object)
+    for l in range(limbs.shape[1] - 1, -1, -1):
+        acc = acc * (1 << bits) + part[:, l].astype(object)
+    return acc
+
+
+def xv_exact_misses(got, G, miss, mu, sinv, val, center, scale, impute, rows, clamp20=False):
+    """Rows (of `rows`) where got_i is farther from the exact X beta than the a-priori forward bound allows.
+
+        exact_i = sum_t (g_it - mu_t) sinv_t v_t      in rational arithmetic over the doubles mu, sinv, v
+                  (no mu term without center, sinv = 1 without scale; a missing entry counts as mu_t with impute, else as dosage 0)
+        |got_i - exact_i| <= (nnz + 20) 2^-53 S_i,    S_i = sum_t (g_it + |mu_t|) |sinv_t v_t|
+
+    -- a chain of nnz multiply-adds and at most 16 group additions (which also cover the centring and fix-up terms); nothing of
+    it is measured.  Everything is a dyadic rational, so the comparison itself is done in integers: no rounding on the checking
+    side.  clamp20: got is compared with clip(exact, -20, 20) (clipping moves two numbers no farther apart).
+    G (n x nnz) stored dosages in list order (0 where missing), miss (n x nnz) bool.  Returns [(row, got, exact as float, bound as float)]."""
+    from fractions import Fraction
+    rows = np.asarray(rows, dtype=np.int64)
+    nnz = G.shape[1]
+    if nnz == 0:
+        return [(int(i), float(got[i]), 0.0, 0.0) for i in rows if got[i] != 0.0]
+    W = [(Fraction(float(s)) if scale else Fraction(1)) * Fraction(float(v)) for s, v in zip(sinv, val)]
+    Cm = [Fraction(float(m_)) * w for m_, w in zip(mu, W)]
+    D = max(max(f.denominator for f in W), max(f.denominator for f in Cm))           # powers of two: the largest is the common one
+    Wn = [int(f * D) for f in W]; Cn = [int(f * D) for f in Cm]
+    Gr, Mr = np.asarray(G)[rows], np.asarray(miss)[rows]
+    N = _int_matvec(Gr, Wn)
+    if center:
+        N = N - sum(Cn)
+    if impute and Mr.any():
+        N = N + _int_matvec(Mr, Cn)
+    S = _int_matvec(Gr, [abs(v) for v in Wn]) + sum(abs(v) for v in Cn)
+    bad = []
+    for r, i in enumerate(rows):
+        num = int(N[r])
+        if clamp20:
+            num = max(-20 * D, min(20 * D, num))
+        gp, gq = float(got[i]).as_integer_ratio()
+        if (abs(gp * D - num * gq) << 53) > (nnz + 20) * int(S[r]) * gq:
+            bad.append((int(i), float(got[i]), num / D, (nnz + 20) * 2.0 ** -53 * (int(S[r]) / D)))
+    return bad
+
+
 
 # ---- the 16-bit dosage matrix: the standardized matrix, an edge-case matrix, exact X'r and X beta, the counted error bounds ----
 def standardized(num, den, mu, sinv):
