@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf); 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -121,6 +121,42 @@ enum {
 };
 int mih_dosage_create_bgen(const char *path, int64_t n, int64_t ncols, const int64_t *block_offset, int compression,
                            int threads, int device, mih_mat **out, int32_t *denom_out, int64_t *bad_block, int32_t *bad_what);
+/* A dosage handle built straight from a VCF file, plain text, gzip (one or several members) or BGZF; the GPU tokenises the
+ * sample fields.  mih_vcf_open needs no device: it finds the container from the file's bytes (a name ending in .gz must hold
+ * gzip, any other name text), scans the inflated text once -- BGZF blocks inflated by `threads` workers (0: the library's
+ * default; at most 8 in this pass either way), a gzip stream serially -- for the one #CHROM line (n = its fields - 9), the number of records (lines
+ * that do not start with '#') and the longest line, and cuts the text into chunks of whole lines of at most
+ * max(chunk_bytes, longest line) bytes (chunk_bytes = 0: 8 MB), the unit pass 2 stages.  mih_dosage_create_vcf streams records
+ * [rec0, rec0 + nrec) into an n x nrec matrix: field 0 reads GT (one or two alleles of 0 1 . separated by / or |; the count of
+ * 1s over the denominator 1), field 1 reads DS (D+, D+., D+.D*, .D+; at most 4 decimals once trailing zeros are dropped, at most 2,
+ * at most 32 bytes) on the grid 10^4 / g, g the gcd of 10^4 and every positive numerator: numerators and *denom_out as
+ * genotypes.genotype_values gives them for these records.  The key's place in FORMAT is found per record; a sample field that
+ * ends before it, an empty token and '.' are missing (0xFFFF).  mih_vcf_meta: CHROM POS ID REF ALT of the records just read,
+ * tab-separated, one line each; mih_vcf_header: the #CHROM line.  Both copy at most len bytes and report the full length in
+ * *need.  Whatever is outside this (MIH_VCF_*) is refused with MIH_BAD_ARG, nothing left allocated or open, *bad_record the
+ * least 0-based record index found bad and *bad_what why: a reader hands such a file to its general path. */
+enum {
+    MIH_VCF_RAGGED = 1,         /* a record without exactly 9 + n tab-separated fields (an empty line is one) */
+    MIH_VCF_TOKEN = 2,          /* a token outside the grammar; a '\r' or a non-ASCII byte in a record; POS not all digits */
+    MIH_VCF_RANGE = 3,          /* a DS value above 2 */
+    MIH_VCF_DECIMALS = 4,       /* a fifth significant decimal */
+    MIH_VCF_NOKEY = 5,          /* FORMAT does not hold the wanted key */
+    MIH_VCF_MULTIALLELIC = 6,   /* a comma in ALT */
+    MIH_VCF_HEADER = 7,         /* no #CHROM line before the first record, a second one, a '\r' in a # line, no sample column */
+    MIH_VCF_CONTAINER = 8,      /* the bytes are not what the name says; a member that does not inflate or is truncated */
+    MIH_VCF_IO = 9              /* not a regular file that can be opened and read (missing, a directory, a pipe), or one that changed */
+};
+typedef struct mih_vcf mih_vcf;
+int mih_vcf_open(const char *path, int threads, int64_t chunk_bytes, mih_vcf **out, int64_t *bad_record, int32_t *bad_what);
+int mih_vcf_info(const mih_vcf *v, int64_t *n, int64_t *nrecords, int32_t *container /* 0 text, 1 gzip, 2 BGZF */, int64_t *longest_line);
+int mih_vcf_header(const mih_vcf *v, char *buf, int64_t len, int64_t *need);
+int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int device, mih_mat **out,
+                          int32_t *denom_out, int64_t *bad_record, int32_t *bad_what);
+int mih_vcf_meta(const mih_vcf *v, char *buf, int64_t len, int64_t *need);
+/* The host work of mih_dosage_create_vcf alone, for measurements: the same workers read and inflate every chunk of the file
+ * into ordinary memory and drop it -- no device, no look at the text.  *bytes: the inflated bytes. */
+int mih_vcf_inflate(const mih_vcf *v, int threads, int64_t *bytes);
+int mih_vcf_close(mih_vcf *v);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

@@ -151,6 +151,13 @@ def lib():
         "mih_dosage_export": [vp, i64, i64, vp],
         "mih_dosage_create_bgen": [C.c_char_p, i64, i64, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64),
                                    C.POINTER(i32)],
+        "mih_vcf_open": [C.c_char_p, C.c_int, i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32)],
+        "mih_vcf_info": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)],
+        "mih_vcf_header": [vp, C.c_char_p, i64, C.POINTER(i64)],
+        "mih_dosage_create_vcf": [vp, C.c_int, i64, i64, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)],
+        "mih_vcf_meta": [vp, C.c_char_p, i64, C.POINTER(i64)],
+        "mih_vcf_inflate": [vp, C.c_int, C.POINTER(i64)],
+        "mih_vcf_close": [vp],
         "mih_dosage_regrid": [vp, i32],
         "mih_mat_destroy": [vp],
         "mih_mat_dims": [vp, C.POINTER(i64), C.POINTER(i64)],
@@ -210,7 +217,8 @@ def exported_symbols():
             "mih_snp_create_synthetic_shard",
             "mih_dense_create", "mih_dense_create_synthetic", "mih_dense_create_f32",
             "mih_dosage_create", "mih_dosage_create_synthetic", "mih_dosage_export",
-            "mih_dosage_create_bgen", "mih_dosage_regrid", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
+            "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
+            "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",

@@ -391,7 +391,7 @@ int mih_last_error(char *buf, size_t len)
 int mih_version(int *major, int *minor)
 {
     if (major) *major = 0;
-    if (minor) *minor = 6;        // 0.6: mih_dosage_create_bgen, mih_dosage_regrid; 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
+    if (minor) *minor = 7;        // 0.7: mih_vcf_*, mih_dosage_create_vcf; 0.6: mih_dosage_create_bgen, mih_dosage_regrid; 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
     return MIH_OK;
 }
 

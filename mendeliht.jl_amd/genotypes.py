@@ -315,7 +315,7 @@ class BgenIndex:
 
 
 class _NotStreamable(ArgumentError):
-    """A BGEN file the streamed reader does not take: parse_genotypes reads it with read_bgen instead."""
+    """A BGEN or VCF file the streamed reader does not take: parse_genotypes reads it with read_bgen / read_vcf instead."""
 
 
 def _bgen_walk(path, sample_path=None, stop=None):
@@ -425,6 +425,71 @@ def read_bgen_device(path, sample_path=None, variants=None, threads=None, device
     return x, idx.samples, idx.chrom[a:e], idx.pos[a:e], idx.ids[a:e], idx.ref[a:e], idx.alt[a:e]
 
 
+# ---- VCF, streamed -----------------------------------------------------------------------------
+def _vcf_text(fn, v):
+    """The text a mih_vcf_header / mih_vcf_meta call holds, as bytes."""
+    import ctypes as C
+    need = C.c_int64(0)
+    fn(v, None, 0, C.byref(need))
+    buf = C.create_string_buffer(max(need.value, 1))
+    fn(v, buf, need.value, C.byref(need))
+    return buf.raw[:need.value]
+
+
+def read_vcf_device(path, dosage=False, variants=None, threads=None, device=0, chunk_bytes=None):
+    """read_vcf's 7-tuple with a DosageMatrix in place of the columns, streamed from the file into the device: plain text, gzip
+    or BGZF (found from the bytes), host threads read and inflate, the GPU tokenises the sample fields (mih_vcf_open,
+    mih_dosage_create_vcf).  The matrix is the one DosageMatrix(*genotype_values(read_vcf(path, dosage)[0])) holds, bit for
+    bit.  `variants`: a contiguous range of 0-based record indices (a column shard) on its own reduced grid, the metadata of
+    those records returned.  `chunk_bytes`: the text staged per transfer (default 8 MB; at least the longest line).  A file
+    this path does not take -- anything but GT alleles 0 1 . and plain decimals of at most 4 places up to 2, ragged or
+    multi-allelic records, '\r', header or container trouble, a path that is no readable regular file -- raises _NotStreamable, naming the 1-based record and the reason:
+    parse_genotypes reads such a file with read_vcf, whose results and errors stay what they are."""
+    import ctypes as C
+
+    from .api import _check, lib
+    path = str(path)
+    if variants is not None and (not isinstance(variants, range) or variants.step != 1):
+        raise ArgumentError("variants must be a contiguous range of 0-based record indices")
+    L = lib()
+    v, br, bw = C.c_void_p(None), C.c_int64(-1), C.c_int32(0)
+
+    def cannot():                       # the library's own words: "path: record N: reason"
+        buf = C.create_string_buffer(1024)
+        L.mih_last_error(buf, 1024)
+        return _NotStreamable(f"{buf.value.decode(errors='replace')}: not streamed")
+    rc = L.mih_vcf_open(os.fsencode(path), int(threads or 0), int(chunk_bytes or 0), C.byref(v), C.byref(br), C.byref(bw))
+    if rc != 0 and bw.value:
+        raise cannot()
+    _check(rc)
+    try:
+        n, m = C.c_int64(0), C.c_int64(0)
+        _check(L.mih_vcf_info(v, C.byref(n), C.byref(m), None, None))
+        a, e = (0, m.value) if variants is None else (variants.start, variants.stop)
+        if not 0 <= a <= e <= m.value:
+            raise ArgumentError(f"variants {variants} out of range for {m.value} records")
+        if m.value == 0:
+            raise _NotStreamable(f"{path} holds no variants")
+        if a == e:
+            raise ArgumentError(f"variants {variants} is empty")
+        try:
+            samples = _vcf_text(L.mih_vcf_header, v).decode("ascii").split("\t")[9:]
+        except UnicodeDecodeError:
+            raise _NotStreamable(f"{path}: record 1: sample ids that are not ASCII: not streamed") from None
+        h, den = C.c_void_p(None), C.c_int32(0)
+        rc = L.mih_dosage_create_vcf(v, 1 if dosage else 0, a, e - a, int(threads or 0), device, C.byref(h), C.byref(den),
+                                     C.byref(br), C.byref(bw))
+        if rc != 0 and bw.value:
+            raise cannot()
+        _check(rc)
+        x = DosageMatrix(None, den.value, device=device, _handle=h)
+        rows = [ln.split("\t") for ln in _vcf_text(L.mih_vcf_meta, v).decode("ascii").split("\n")[:-1]]
+    finally:
+        L.mih_vcf_close(v)
+    chrom, pos, ids, ref, alt = ([r[k] for r in rows] for k in range(5))
+    return x, samples, chrom, [int(q) for q in pos], ids, ref, alt
+
+
 # ---- parse_genotypes ---------------------------------------------------------------------------
 def parse_genotypes(tgtfile, dosage=False, device=0):
     """parse_genotypes(tgtfile, dosage) -- wrapper.jl:451-485: (X, sample_ids, chr, pos, snpid, ref, alt).  VCF (`.vcf`,
@@ -433,7 +498,10 @@ def parse_genotypes(tgtfile, dosage=False, device=0):
     SnpLinAlg(center=true, scale=true, impute=true).  Either way X is the standardized matrix the reference fits."""
     tgt = str(tgtfile)
     if tgt.endswith((".vcf", ".vcf.gz")):
-        cols, samples, chrom, pos, ids, ref, alt = read_vcf(tgt, dosage)
+        try:
+            return read_vcf_device(tgt, dosage, device=device)
+        except _NotStreamable:          # read_vcf's own path: whatever is outside the streamed grammar, and its errors
+            cols, samples, chrom, pos, ids, ref, alt = read_vcf(tgt, dosage)
     elif tgt.endswith(".bgen"):
         try:
             return read_bgen_device(tgt, device=device)
