@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf); 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf: additions, the version stays); 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -144,7 +144,8 @@ enum {
     MIH_VCF_MULTIALLELIC = 6,   /* a comma in ALT */
     MIH_VCF_HEADER = 7,         /* no #CHROM line before the first record, a second one, a '\r' in a # line, no sample column */
     MIH_VCF_CONTAINER = 8,      /* the bytes are not what the name says; a member that does not inflate or is truncated */
-    MIH_VCF_IO = 9              /* not a regular file that can be opened and read (missing, a directory, a pipe), or one that changed */
+    MIH_VCF_IO = 9,             /* not a regular file that can be opened and read (missing, a directory, a pipe), or one that changed */
+    MIH_VCF_NOT_HARD_CALL = 10  /* mih_snp_create_vcf only: a DS value other than 0, 1 or 2 (the 2-bit matrix holds hard calls) */
 };
 typedef struct mih_vcf mih_vcf;
 int mih_vcf_open(const char *path, int threads, int64_t chunk_bytes, mih_vcf **out, int64_t *bad_record, int32_t *bad_what);
@@ -157,6 +158,36 @@ int mih_vcf_meta(const mih_vcf *v, char *buf, int64_t len, int64_t *need);
  * into ordinary memory and drop it -- no device, no look at the text.  *bytes: the inflated bytes. */
 int mih_vcf_inflate(const mih_vcf *v, int threads, int64_t *bytes);
 int mih_vcf_close(mih_vcf *v);
+/* Hard calls in a dosage handle -- every numerator 0, denom, 2 denom or 0xFFFF, which is what a VCF GT field and a hard-call
+ * BGEN file give -- packed on the device into the 2-bit matrix of mih_snp_create: a quarter of a byte per genotype instead of
+ * two, and the matrix-core X'r pass, the 19-residual fused pass and the resident IHT step instead of the dense kernels.  The
+ * dosage counts ALT alleles as .bed counts allele 2, so the result is, bit for bit, the handle mih_snp_create builds from the
+ * .bed codes 0 -> 00, 1 -> 10, 2 -> 11, missing -> 01 of the same genotypes (image, mu, sinv, missing lists; an all-missing
+ * column is whatever mih_snp_create makes of it).  center, scale, impute, dtype: as mih_snp_create.
+ *
+ * A builder takes the matrix panel by panel, so that n x p u16 never has to exist: mih_snp_builder_create allocates the n x p
+ * image, mih_snp_builder_add packs a dosage handle of n rows into columns [col0, col0 + dosage.p) -- panels in any order, col0
+ * any column (two panels may share a group of 32 columns: a pack writes only the 16-byte lane records of its own columns); the
+ * call returns when the panel has been read, and the panel may be destroyed -- and mih_snp_builder_finish, once every column has
+ * been added, computes the statistics and the missing lists and hands out an ordinary immutable matrix handle (with the reserve
+ * rule of mih_snp_create); the builder is then empty and is still to be destroyed.  mih_snp_builder_destroy releases whatever the
+ * builder still owns, at any point.  Refusals: a panel with another row count or columns outside the matrix MIH_BAD_DIM; a column
+ * added twice, or a numerator that is no hard call, MIH_BAD_ARG with *bad_col (may be NULL) the least offending 0-based column
+ * of the matrix and a message naming it 1-based; finish with columns missing MIH_BAD_ARG.  After a numerator has been refused
+ * the builder accepts nothing more and cannot finish.  mih_snp_create_dosage is create + one add + finish. */
+typedef struct mih_snp_builder mih_snp_builder;
+int mih_snp_builder_create(int64_t n, int64_t p, int center, int scale, int impute, int dtype, int device, mih_snp_builder **out);
+int mih_snp_builder_add(mih_snp_builder *b, int64_t col0, const mih_mat *dosage, int64_t *bad_col);
+int mih_snp_builder_finish(mih_snp_builder *b, mih_mat **out);
+int mih_snp_builder_destroy(mih_snp_builder *b);
+int mih_snp_create_dosage(const mih_mat *dosage, int center, int scale, int impute, int dtype, mih_mat **out, int64_t *bad_col);
+/* Records [rec0, rec0 + nrec) of an opened VCF file streamed straight into the 2-bit matrix: pass 2 of mih_dosage_create_vcf
+ * with the tokeniser pointed at a per-worker u16 panel of the chunk's records and the pack queued behind it on the worker's
+ * stream, so device memory holds the 2-bit image and the workers' staging, never n x nrec u16.  field 0: GT; field 1: DS where
+ * every value is exactly 0, 1 or 2 (any spelling the DS grammar takes).  A record with another DS value is refused as
+ * MIH_VCF_NOT_HARD_CALL; every other refusal, and mih_vcf_meta afterwards, are mih_dosage_create_vcf's. */
+int mih_snp_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int center, int scale, int impute, int dtype,
+                       int device, mih_mat **out, int64_t *bad_record, int32_t *bad_what);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

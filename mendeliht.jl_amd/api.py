@@ -159,6 +159,13 @@ def lib():
         "mih_vcf_inflate": [vp, C.c_int, C.POINTER(i64)],
         "mih_vcf_close": [vp],
         "mih_dosage_regrid": [vp, i32],
+        "mih_snp_builder_create": [i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
+        "mih_snp_builder_add": [vp, i64, vp, C.POINTER(i64)],
+        "mih_snp_builder_finish": [vp, C.POINTER(vp)],
+        "mih_snp_builder_destroy": [vp],
+        "mih_snp_create_dosage": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i64)],
+        "mih_snp_create_vcf": [vp, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i64),
+                               C.POINTER(i32)],
         "mih_mat_destroy": [vp],
         "mih_mat_dims": [vp, C.POINTER(i64), C.POINTER(i64)],
         "mih_mat_reserve": [vp, i64],
@@ -218,7 +225,8 @@ def exported_symbols():
             "mih_dense_create", "mih_dense_create_synthetic", "mih_dense_create_f32",
             "mih_dosage_create", "mih_dosage_create_synthetic", "mih_dosage_export",
             "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
-            "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
+            "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
+            "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
@@ -497,6 +505,64 @@ class SnpLinAlg(_Mat):
         return out
 
 
+def _snp_dtype(dtype):
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float64, np.float32):
+        raise ArgumentError("SnpLinAlg{T}: T must be Float64 or Float32")
+    return dtype
+
+
+class SnpBuilder:
+    """A SnpLinAlg built on the device from hard-call DosageMatrix panels (mih_snp_builder_*): add(col0, panel) packs the
+    panel's columns into columns col0 .. of the 2-bit image -- in any order, at any col0 -- and finish() returns the SnpLinAlg
+    once every column is there.  Device memory holds the 2-bit image and the panel in hand, never n x p numerators."""
+
+    def __init__(self, n, p, center=True, scale=True, impute=True, dtype=np.float64, device=0):
+        self._b = C.c_void_p(None)
+        self.n, self.p, self.device = int(n), int(p), device
+        self._flags = (bool(center), bool(scale), bool(impute), _snp_dtype(dtype))
+        self.bad_col = -1
+        _check(lib().mih_snp_builder_create(self.n, self.p, int(center), int(scale), int(impute),
+                                            32 if self._flags[3] is np.float32 else 64, device, C.byref(self._b)))
+
+    def add(self, col0, panel):
+        """Columns [col0, col0 + panel.p) from a DosageMatrix whose entries are all 0, 1, 2 or missing."""
+        if not isinstance(panel, DosageMatrix):
+            raise ArgumentError("a panel must be a DosageMatrix")
+        if not self._b:
+            raise ArgumentError("the builder is closed")
+        bad = C.c_int64(-1)
+        rc = lib().mih_snp_builder_add(self._b, int(col0), panel._h, C.byref(bad))
+        self.bad_col = bad.value            # the least column (0-based, of the whole matrix) a refusal names, else -1
+        _check(rc)
+        return self
+
+    def finish(self, reserve=None):
+        if not self._b:
+            raise ArgumentError("the builder is closed")
+        h = C.c_void_p(None)
+        try:
+            _check(lib().mih_snp_builder_finish(self._b, C.byref(h)))
+        finally:
+            if h:
+                self.close()
+        center, scale, impute, dtype = self._flags
+        x = SnpLinAlg(None, center=center, scale=scale, impute=impute, device=self.device, _handle=h, dtype=dtype)
+        x._reserve(reserve)
+        return x
+
+    def close(self):
+        if self._b:
+            lib().mih_snp_builder_destroy(self._b)
+            self._b = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def naive_impute(x, destination, n=None):
     """naive_impute(x::SnpArray, destination) -- src/utilities.jl:862-899: writes `destination` (.bed) with every missing
     genotype of `x` replaced by the mode of its SNP.  `x` is a PLINK .bed path or the (p, ceil(n/4)) column bytes (then
@@ -608,6 +674,18 @@ class DosageMatrix(_Mat):
         _check(lib().mih_dosage_regrid(self._h, int(denom)))
         self.denom = int(denom)
         return self
+
+    def to_snp(self, center=True, scale=True, impute=True, dtype=np.float64, reserve=None):
+        """The SnpLinAlg of a matrix of hard calls -- every entry 0, 1, 2 or missing, whatever the denominator -- packed on the
+        device (mih_snp_create_dosage): bit for bit the SnpLinAlg of the .bed encoding of the same genotypes (ALT counted as
+        allele 2), at a quarter of a byte per genotype.  ArgumentError naming the first column that holds anything else."""
+        dtype = _snp_dtype(dtype)
+        h = C.c_void_p(None)
+        _check(lib().mih_snp_create_dosage(self._h, int(center), int(scale), int(impute), 32 if dtype is np.float32 else 64,
+                                           C.byref(h), None))
+        x = SnpLinAlg(None, center=center, scale=scale, impute=impute, device=self.device, _handle=h, dtype=dtype)
+        x._reserve(reserve)
+        return x
 
     def export(self, col0=0, ncols=None):
         """Numerators of columns [col0, col0 + ncols) as an n x ncols uint16 array (0xFFFF = missing)."""
@@ -1352,14 +1430,15 @@ def _read_bim(prefix):
     return chrom, pos, ids, a1, a2
 
 
-def _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx=(), dosage=False, device=0):
-    """x, y, z and the variants' (chr, pos, SNPid, ref, alt) of iht / cross_validate (wrapper.jl:64-79)."""
+def _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx=(), dosage=False, device=0, two_bit=False):
+    """x, y, z and the variants' (chr, pos, SNPid, ref, alt) of iht / cross_validate (wrapper.jl:64-79).  two_bit: a VCF or
+    BGEN file of hard calls becomes a SnpLinAlg (parse_genotypes)."""
     if str(plinkfile).endswith((".vcf", ".vcf.gz", ".bgen")):
         from .genotypes import parse_genotypes
         if not isinstance(phenotypes, (str, os.PathLike)):
             raise ArgumentError("VCF / BGEN inputs carry no phenotypes: give `phenotypes` as a comma-separated file, one sample "
                                 "per row (wrapper.jl:210-224)")
-        x, _ids, chrom, pos, snpid, ref, alt = parse_genotypes(plinkfile, dosage=dosage, device=device)
+        x, _ids, chrom, pos, snpid, ref, alt = parse_genotypes(plinkfile, dosage=dosage, device=device, two_bit=two_bit)
         y = parse_phenotypes(plinkfile, phenotypes, d, x.n)
         if np.shape(y)[-1] != x.n:
             raise DimensionMismatch(f"{phenotypes} has {np.shape(y)[-1]} samples, {plinkfile} has {x.n}")
@@ -1398,16 +1477,17 @@ def _show_result(io, res):
 
 
 def iht(plinkfile, k, d, *, phenotypes=6, covariates="", summaryfile="iht.summary.txt", betafile="iht.beta.txt",
-        covariancefile="iht.cov.txt", exclude_std_idx=(), dosage=False, device=0, **kwargs):
+        covariancefile="iht.cov.txt", exclude_std_idx=(), dosage=False, device=0, two_bit=False, **kwargs):
     """iht(filename, k, d; phenotypes, covariates, summaryfile, betafile, covariancefile, exclude_std_idx, dosage, kwargs...) --
     src/wrapper.jl:52-120 for binary PLINK input: SnpLinAlg{Float64}(center=true, scale=true, impute=true) on the GPU, the
     reference's phenotype / covariate parsing, fit_iht with the canonical link (LogLink for NegativeBinomial, wrapper.jl:87),
     the summary file (the fit's log + show(result)) and the beta file `chr pos SNPid ref alt Estimated_beta` (one row per SNP,
     tab-separated; `beta_1 .. beta_r` columns and the covariance file for multivariate traits, wrapper.jl:100-116).  (v1.4.11
     then overwrites the beta file with an empty CSV header, wrapper.jl:117 `CSV.write(betafile, df)` on an empty DataFrame;
-    that accident is not reproduced.)"""
+    that accident is not reproduced.)  two_bit=True: a VCF or BGEN file of hard calls is packed into the 2-bit SnpLinAlg and
+    fitted exactly as the PLINK trio of the same genotypes; a file that holds anything else is an ArgumentError."""
     d = _inst(d)
-    x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device)
+    x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device, two_bit)
     mv = _is_multivariate(y)
     user_io = kwargs.pop("io", None)
     with open(summaryfile, "w") if summaryfile else open(os.devnull, "w") as io:
@@ -1444,12 +1524,13 @@ def print_cv_results(io, errors, path, k):
 
 
 def cross_validate(plinkfile, d, *, path=range(1, 21), q=5, phenotypes=6, covariates="",
-                   cv_summaryfile="cviht.summary.txt", exclude_std_idx=(), dosage=False, device=0, **kwargs):
+                   cv_summaryfile="cviht.summary.txt", exclude_std_idx=(), dosage=False, device=0, two_bit=False, **kwargs):
     """cross_validate(filename, d; path, phenotypes, covariates, cv_summaryfile, q, exclude_std_idx, dosage, kwargs...) --
-    src/wrapper.jl:301-349 for binary PLINK input; the summary file is print_cv_results + the total time, as the reference's."""
+    src/wrapper.jl:301-349 for binary PLINK input; the summary file is print_cv_results + the total time, as the reference's.
+    two_bit: as iht."""
     t0 = time.time()
     d = _inst(d)
-    x, y, z, _info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device)
+    x, y, z, _info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device, two_bit)
     path = list(path)
     if _is_multivariate(y):
         mse = cv_iht(y, x, z.T, d=MvNormal(), path=path, q=q, **kwargs)

@@ -356,6 +356,13 @@ __device__ __forceinline__ double dosage_x(const DosageView &v, int64_t j, int64
 {
     return dosage_c(v.X[j * v.ld + i], v.mun[j]) * v.sc[j];
 }
+// snp.hip: the pack of an n-row u16 hard-call panel (column stride ld, a multiple of 8; hard-call unit `unit`) into columns
+// [col0, col0 + ncols) of a builder's 2-bit image, queued on stream s -- no bookkeeping, so workers may call it side by side on
+// streams of their own.  A column that is no hard call leaves (bad_base + its index in the panel) << bad_shift | bad_low in
+// *bad (an atomic min).  snp_builder_cover_all: every column has been delivered this way.
+int snp_builder_pack(mih_snp_builder *b, int64_t col0, int64_t ncols, const uint16_t *panel, int64_t ld, uint32_t unit,
+                     unsigned long long *bad, unsigned long long bad_base, int bad_shift, unsigned long long bad_low, hipStream_t s);
+void snp_builder_cover_all(mih_snp_builder *b);
 constexpr int kWorkerStreamsPerLane = 4;       // the runtime maps streams onto a handful of hardware queues anyway
 // stream i of the matrix's worker set (i < 2 * kWorkerStreamsPerLane); nullptr if it cannot be created
 hipStream_t worker_stream(const mih_mat *h, int i);

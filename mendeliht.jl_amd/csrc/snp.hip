@@ -103,6 +103,66 @@ k_transcode(const uint8_t *__restrict__ raw, int64_t raw_stride, int64_t n, int6
     flush_counts(c1, c2, cm, cg, p, cnt);
 }
 
+// ---- 16-bit hard calls -> the tile-major image ------------------------------------------------------------------------------
+// The sibling of k_transcode for a column-major u16 panel (column stride ld, a multiple of 8; 0xFFFF = missing): a numerator is a
+// hard call iff it is 0, unit or 2 unit, and becomes the dosage code 0, 1, 2 (missing: the temporary code 3, as k_transcode leaves
+// it for k_missing_from_tiles).  grid (chunks of 64 block pairs, columns of the panel): a workgroup packs one column, so a panel
+// of a few long columns (a VCF chunk) fills its waves as well as a wide one.  Per iteration a wave reads 1 KB of the column in one
+// coalesced 16-byte load per lane -- four block pairs, 16 lanes each, lane l of a unit holding rows 8 l .. 8 l + 7 of its block
+// pair as 16 bits of codes.  Row 8 l is 64 e + 32 h + 16 u + 8 half with l = 8 e + 4 h + 2 u + half: two neighbours make the
+// dword (e, h, u), and the lane records h = 0, 1 gather their four dwords from lanes 4 h + {0, 2, 8, 10} of the unit and leave as one
+// 16-byte store each.  The panel holds columns [col0, col0 + gridDim.y) of the matrix, col0 any column: ONLY the lane records
+// of those columns are written -- two panels packed on different streams may share a group of 32 columns, and a column's records
+// are 16-byte words of its own.  Rows >= n of a record are zeros whatever the panel holds there.  A column that holds anything
+// else reports (bad_base + its index in the panel) << bad_shift | bad_low through an atomicMin.
+__global__ void __launch_bounds__(256)
+k_pack_u16(const uint16_t *__restrict__ src, int64_t ld, int64_t n, int64_t col0, uint32_t unit,
+           uint4 *__restrict__ X, int64_t nbp, int32_t *__restrict__ cnt, unsigned long long *__restrict__ bad,
+           unsigned long long bad_base, int bad_shift, unsigned long long bad_low)
+{
+    __shared__ int32_t red[3];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, sub = lane >> 4, l = lane & 15, h = l & 1;
+    const int64_t jl = blockIdx.y, j = col0 + jl, cg = j >> 5;
+    const int m = (int)(j & 31);
+    const uint16_t *col = src + jl * ld;
+    const uint32_t two = 2u * unit;
+    if (threadIdx.x < 3) red[threadIdx.x] = 0;
+    __syncthreads();
+    int32_t c1 = 0, c2 = 0, cm = 0;
+    bool wrong = false;
+    const int64_t bp0 = (int64_t)blockIdx.x * kBpPerBlock;
+    for (int64_t b = bp0 + 4 * w; b < bp0 + kBpPerBlock && b < nbp; b += 16) {      // (the same trips for every lane of a wave)
+        const int64_t bp = b + sub, rr = bp * 128 + 8 * l;
+        uint32_t bits = 0;
+        if (rr < n) {                                            // (rr < n <= ld, both multiples of 8: the load stays inside the column)
+            const uint4 v4 = *reinterpret_cast<const uint4 *>(col + rr);
+            const uint32_t vw[4] = {v4.x, v4.y, v4.z, v4.w};
+            #pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t v = (vw[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+                const uint32_t code = v == 0xFFFFu ? 3u : (v == unit ? 1u : (v == two ? 2u : 0u));
+                if (rr + k < n) {
+                    wrong |= v != 0u && code == 0u;
+                    bits |= code << (2 * k);
+                }
+            }
+        }
+        const uint32_t mm = bits & (bits >> 1) & 0x5555u, dd = bits & ~(mm | (mm << 1));
+        c1 += __popc(dd & 0x5555u); c2 += __popc(dd & 0xAAAAu); cm += __popc(mm);
+        const uint32_t other = __shfl_xor(bits, 1, 64);
+        const uint32_t dw = h ? (other | (bits << 16)) : (bits | (other << 16));    // both lanes of a pair hold the pair's 16 rows
+        const int from = (lane & 48) + 4 * h;                    // lanes l = 0, 1 of a unit write the records h = 0, 1
+        const uint32_t d0 = __shfl(dw, from, 64), d1 = __shfl(dw, from + 2, 64), d2 = __shfl(dw, from + 8, 64), d3 = __shfl(dw, from + 10, 64);
+        if (l < 2 && bp < nbp) X[(cg * nbp + bp) * 64 + h * 32 + m] = make_uint4(d0, d1, d2, d3);
+    }
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { c1 += __shfl_xor(c1, off, 64); c2 += __shfl_xor(c2, off, 64); cm += __shfl_xor(cm, off, 64); }
+    if (lane == 0) { atomicAdd(&red[0], c1); atomicAdd(&red[1], c2); atomicAdd(&red[2], cm); }
+    __syncthreads();
+    if (threadIdx.x < 3 && red[threadIdx.x]) atomicAdd(&cnt[3 * j + threadIdx.x], red[threadIdx.x]);
+    if (__ballot(wrong) != 0ull && lane == 0) atomicMin(bad, ((bad_base + (unsigned long long)jl) << bad_shift) | bad_low);
+}
+
 // mu_j = (n1 + 2 n2) / (n - nmiss); sinv_j = 1/sqrt(mu(1-mu/2)) if that sqrt > 0 else 1
 __global__ void k_col_stats(const int32_t *__restrict__ cnt, int64_t n, int64_t p,
                             double *__restrict__ mu, double *__restrict__ sinv)
@@ -325,6 +385,23 @@ static int finish_missing_ptr(mih_mat *h, const std::vector<int32_t> &cnt, std::
     return MIH_OK;
 }
 
+// What follows the last transcode (or pack) of a matrix: mu and sinv from the per-column counts, the missing lists, and the
+// tiles' temporary code 3 turned into dosage 0.
+static int finish_tiles(mih_mat *h, const int32_t *cnt_dev)
+{
+    const int64_t p = h->p;
+    hipLaunchKernelGGL(k_col_stats, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, h->stream, cnt_dev, h->n, p, h->mu, h->sinv);
+    std::vector<int32_t> hcnt((size_t)(3 * p));
+    if (hipMemcpy(hcnt.data(), cnt_dev, sizeof(int32_t) * hcnt.size(), hipMemcpyDeviceToHost) != hipSuccess) return MIH_HIP_ERROR;
+    std::vector<int64_t> ptr;
+    MIH_TRY(finish_missing_ptr(h, hcnt, ptr));
+    if (h->total_missing > 0)
+        hipLaunchKernelGGL(k_missing_from_tiles, dim3((unsigned)h->ncg), dim3(64), 0, h->stream, reinterpret_cast<uint4 *>(h->X), h->nbp, p,
+                           h->miss_ptr, h->miss_row);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return MIH_HIP_ERROR;
+    return MIH_OK;
+}
+
 static int alloc_snp(mih_mat *h)
 {
     h->ncg = (h->p + 31) / 32;
@@ -369,6 +446,48 @@ int select_device(int device)
 
 using namespace mih;
 
+// A 2-bit matrix under construction from 16-bit hard-call panels (mih_snp_builder_*): the image, the per-column counters the
+// pack kernels add to, and which columns have been delivered.  The finished matrix leaves it as an ordinary immutable handle.
+struct mih_snp_builder {
+    mih_mat *h = nullptr;
+    mih::DevBuf<int32_t> cnt;                  // 3 p: n1, n2, nmiss per column
+    mih::DevBuf<unsigned long long> bad;       // the least offending column of the add in flight
+    std::vector<bool> covered;
+    int64_t ncovered = 0;
+    bool spoilt = false;                       // a refused panel has left counts and records behind: nothing more may be used
+};
+
+namespace mih {
+int snp_builder_pack(mih_snp_builder *b, int64_t col0, int64_t ncols, const uint16_t *panel, int64_t ld, uint32_t unit,
+                     unsigned long long *bad, unsigned long long bad_base, int bad_shift, unsigned long long bad_low, hipStream_t s)
+{
+    const mih_mat *h = b->h;
+    if (col0 < 0 || ncols <= 0 || col0 + ncols > h->p || ld < h->n || ld % 8 != 0 || ((uintptr_t)panel & 15) != 0) {
+        set_error("pack of columns [%lld, %lld): a panel outside the matrix or not 16-byte aligned", (long long)col0, (long long)(col0 + ncols));
+        return MIH_BAD_DIM;
+    }
+    const int64_t slab = 1ll << 15;            // (grid.y stays below 65536)
+    for (int64_t c = 0; c < ncols; c += slab) {
+        const int64_t nc = std::min(slab, ncols - c);
+        dim3 grid((unsigned)((h->nbp + kBpPerBlock - 1) / kBpPerBlock), (unsigned)nc);
+        hipLaunchKernelGGL(k_pack_u16, grid, dim3(256), 0, s, panel + c * ld, ld, h->n, col0 + c, unit, reinterpret_cast<uint4 *>(h->X),
+                           h->nbp, b->cnt.p, bad, bad_base + (unsigned long long)c, bad_shift, bad_low);
+    }
+    // The image comes from hipMalloc uncleared: whoever delivers the last column also zeroes the pad columns of the last group --
+    // lanes p % 32 .. 31 of both halves of every tile, (32 - p % 32) * 16 bytes out of every 512.
+    if (col0 + ncols == h->p && h->p % 32 != 0) {
+        uint4 *first = reinterpret_cast<uint4 *>(h->X) + (h->ncg - 1) * h->nbp * 64 + h->p % 32;
+        MIH_HIP(hipMemset2DAsync(first, 512, 0, (size_t)(32 - h->p % 32) * 16, (size_t)(2 * h->nbp), s));
+    }
+    return MIH_OK;
+}
+void snp_builder_cover_all(mih_snp_builder *b)
+{
+    b->covered.assign((size_t)b->h->p, true);
+    b->ncovered = b->h->p;
+}
+}  // namespace mih
+
 extern "C" {
 
 int mih_device_count(int *count)
@@ -391,7 +510,7 @@ int mih_last_error(char *buf, size_t len)
 int mih_version(int *major, int *minor)
 {
     if (major) *major = 0;
-    if (minor) *minor = 7;        // 0.7: mih_vcf_*, mih_dosage_create_vcf; 0.6: mih_dosage_create_bgen, mih_dosage_regrid; 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
+    if (minor) *minor = 7;        // 0.7: mih_vcf_*, mih_dosage_create_vcf (and, added without a bump, mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf); 0.6: mih_dosage_create_bgen, mih_dosage_regrid; 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
     return MIH_OK;
 }
 
@@ -546,20 +665,111 @@ int mih_snp_create(const uint8_t *bed_cols, int64_t n, int64_t p, int64_t col_st
     if (failed.load()) { set_error("%s", err_msg.c_str()); (void)hipGetLastError(); return fail(MIH_HIP_ERROR); }
     lap("copy + DMA + transcode");
     if (hipStreamSynchronize(h->stream) != hipSuccess) { set_error("transcode kernel failed"); return fail(MIH_HIP_ERROR); }
-    hipLaunchKernelGGL(k_col_stats, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, h->stream, cnt.p, n, p, h->mu, h->sinv);
-    std::vector<int32_t> hcnt((size_t)(3 * p));
-    if (hipMemcpy(hcnt.data(), cnt.p, sizeof(int32_t) * hcnt.size(), hipMemcpyDeviceToHost) != hipSuccess) return fail(MIH_HIP_ERROR);
-    std::vector<int64_t> ptr;
-    if ((rc = finish_missing_ptr(h, hcnt, ptr))) return fail(rc);
-    if (h->total_missing > 0)
-        hipLaunchKernelGGL(k_missing_from_tiles, dim3((unsigned)h->ncg), dim3(64), 0, h->stream, reinterpret_cast<uint4 *>(h->X), h->nbp, p,
-                           h->miss_ptr, h->miss_row);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
+    if ((rc = finish_tiles(h, cnt.p))) return fail(rc);
     lap("statistics + missing lists");
     reserve_fit_memory(h);
     lap("reserve for the fits");
     *out = h;
     return MIH_OK;
+}
+
+int mih_snp_builder_create(int64_t n, int64_t p, int center, int scale, int impute, int dtype, int device, mih_snp_builder **out)
+{
+    if (!out) { set_error("null argument"); return MIH_BAD_ARG; }
+    *out = nullptr;
+    if (n <= 0 || p <= 0) { set_error("bad dimensions n=%lld p=%lld", (long long)n, (long long)p); return MIH_BAD_DIM; }
+    if (n >= (1ll << 31)) { set_error("n must be < 2^31"); return MIH_BAD_DIM; }
+    if (dtype != 64 && dtype != 32) { set_error("dtype must be 64 (SnpLinAlg{Float64}) or 32 (SnpLinAlg{Float32})"); return MIH_BAD_ARG; }
+    MIH_TRY(select_device(device));
+    std::unique_ptr<mih_snp_builder> b(new mih_snp_builder());
+    mih_mat *h = b->h = new mih_mat();
+    h->kind = 0; h->device = device; h->n = n; h->p = p;
+    h->center = center; h->scale = scale; h->impute = impute;
+    auto fail = [&](int code) { mih_mat_destroy(b->h); b->h = nullptr; return code; };
+    int rc = alloc_snp(h);
+    if (rc) return fail(rc);
+    if (hipStreamCreate(&h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
+    if ((rc = b->cnt.alloc((size_t)(3 * p))) || (rc = b->bad.alloc(1))) return fail(rc);
+    if (hipMemsetAsync(b->cnt.p, 0, sizeof(int32_t) * 3 * (size_t)p, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
+    b->covered.assign((size_t)p, false);
+    *out = b.release();
+    return MIH_OK;
+}
+
+int mih_snp_builder_add(mih_snp_builder *b, int64_t col0, const mih_mat *dosage, int64_t *bad_col)
+{
+    if (bad_col) *bad_col = -1;
+    if (!b || !b->h || !dosage || !dosage->Du) { set_error("needs a builder and a dosage handle"); return MIH_BAD_ARG; }
+    if (b->spoilt) { set_error("the builder has refused a panel: nothing more can be added"); return MIH_BAD_ARG; }
+    mih_mat *h = b->h;
+    if (dosage->n != h->n) { set_error("the panel has %lld rows, the matrix %lld", (long long)dosage->n, (long long)h->n); return MIH_BAD_DIM; }
+    if (col0 < 0 || col0 + dosage->p > h->p) {
+        set_error("columns [%lld, %lld) out of range for %lld", (long long)col0, (long long)(col0 + dosage->p), (long long)h->p); return MIH_BAD_DIM;
+    }
+    if (dosage->device != h->device) { set_error("the panel is on device %d, the matrix on %d", dosage->device, h->device); return MIH_BAD_ARG; }
+    for (int64_t j = col0; j < col0 + dosage->p; ++j)
+        if (b->covered[(size_t)j]) {
+            if (bad_col) *bad_col = j;
+            set_error("column %lld has been added before", (long long)(j + 1)); return MIH_BAD_ARG;
+        }
+    MIH_HIP(hipSetDevice(h->device));
+    unsigned long long first = ~0ull;
+    MIH_HIP(hipMemcpyAsync(b->bad.p, &first, sizeof(first), hipMemcpyHostToDevice, h->stream));
+    MIH_TRY(snp_builder_pack(b, col0, dosage->p, dosage->Du, dosage->du_ld, (uint32_t)dosage->denom, b->bad.p, (unsigned long long)col0, 0, 0ull, h->stream));
+    MIH_HIP(hipMemcpyAsync(&first, b->bad.p, sizeof(first), hipMemcpyDeviceToHost, h->stream));
+    MIH_HIP(hipStreamSynchronize(h->stream));
+    if (first != ~0ull) {
+        b->spoilt = true;
+        if (bad_col) *bad_col = (int64_t)first;
+        set_error("column %lld holds a numerator that is not a hard call (0, %d, %d or 0xFFFF over the denominator %d)",
+                  (long long)first + 1, dosage->denom, 2 * dosage->denom, dosage->denom);
+        return MIH_BAD_ARG;
+    }
+    for (int64_t j = col0; j < col0 + dosage->p; ++j) b->covered[(size_t)j] = true;
+    b->ncovered += dosage->p;
+    return MIH_OK;
+}
+
+int mih_snp_builder_finish(mih_snp_builder *b, mih_mat **out)
+{
+    if (!b || !b->h || !out) { set_error("needs a builder that has not finished"); return MIH_BAD_ARG; }
+    *out = nullptr;
+    if (b->spoilt) { set_error("the builder has refused a panel: it cannot finish"); return MIH_BAD_ARG; }
+    if (b->ncovered != b->h->p) {
+        int64_t j = 0;
+        while (b->covered[(size_t)j]) ++j;
+        set_error("%lld of %lld columns have not been added, column %lld the first", (long long)(b->h->p - b->ncovered), (long long)b->h->p, (long long)(j + 1));
+        return MIH_BAD_ARG;
+    }
+    MIH_HIP(hipSetDevice(b->h->device));
+    MIH_TRY(finish_tiles(b->h, b->cnt.p));
+    reserve_fit_memory(b->h);
+    *out = b->h;
+    b->h = nullptr;
+    b->cnt.release();
+    return MIH_OK;
+}
+
+int mih_snp_builder_destroy(mih_snp_builder *b)
+{
+    if (!b) return MIH_OK;
+    if (b->h) { (void)hipSetDevice(b->h->device); (void)hipStreamSynchronize(b->h->stream); mih_mat_destroy(b->h); }
+    delete b;
+    return MIH_OK;
+}
+
+int mih_snp_create_dosage(const mih_mat *dosage, int center, int scale, int impute, int dtype, mih_mat **out, int64_t *bad_col)
+{
+    if (bad_col) *bad_col = -1;
+    if (!dosage || !dosage->Du || !out) { set_error("needs a dosage handle"); return MIH_BAD_ARG; }
+    *out = nullptr;
+    mih_snp_builder *b = nullptr;
+    MIH_TRY(mih_snp_builder_create(dosage->n, dosage->p, center, scale, impute, dtype, dosage->device, &b));
+    int rc = mih_snp_builder_add(b, 0, dosage, bad_col);
+    if (!rc) rc = mih_snp_builder_finish(b, out);
+    mih_snp_builder_destroy(b);
+    return rc;
 }
 
 int mih_snp_create_synthetic(int64_t n, int64_t p, uint64_t seed, double missing_rate,

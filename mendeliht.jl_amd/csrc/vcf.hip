@@ -11,7 +11,8 @@
 // 4 KB segment of a record's sample fields; k_vcf_parse gives every tab its sample index, skips k colons behind it, parses the
 // GT or DS token and writes one u16.  DS numerators are over 10^4; the running gcd of 10^4 and every positive numerator
 // gives the matrix's own reduced grid.  Whatever is outside the grammar is an atomic min of (record, reason): the caller hands the
-// file to the host reader.
+// file to the host reader.  mih_snp_create_vcf is the same pass 2 for hard calls: k_vcf_parse fills a small u16 panel of the chunk's
+// records instead of the matrix, and the pack kernel of snp.hip, queued behind it, writes those columns of a 2-bit image.
 #include "common.h"
 #include <algorithm>
 #include <atomic>
@@ -520,6 +521,7 @@ static const char *vcf_reason(int what)
     case MIH_VCF_MULTIALLELIC: return "a comma in ALT";
     case MIH_VCF_HEADER: return "header lines other than ASCII ## lines and one ASCII #CHROM line before the records";
     case MIH_VCF_IO: return "not a regular file that can be opened and read";
+    case MIH_VCF_NOT_HARD_CALL: return "a DS value other than 0, 1 or 2: not a hard call";
     case MIH_VCF_CONTAINER: return "a container that is not what the file name says, does not inflate or is truncated";
     }
     return "?";
@@ -716,15 +718,21 @@ int mih_vcf_inflate(const mih_vcf *v, int threads, int64_t *bytes)
     return MIH_OK;
 }
 
-int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int device, mih_mat **out,
-                          int32_t *denom_out, int64_t *bad_record, int32_t *bad_what)
+static int vcf_check_args(const mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads)
 {
-    if (!v || !out || !denom_out || !bad_record || !bad_what) { set_error("null argument"); return MIH_BAD_ARG; }
-    *out = nullptr; *bad_record = -1; *bad_what = 0;
     if (field != 0 && field != 1) { set_error("field must be 0 (GT) or 1 (DS), got %d", field); return MIH_BAD_ARG; }
     if (rec0 < 0 || nrec <= 0 || rec0 + nrec > v->nrecords) { set_error("records [%lld, %lld) out of range for %lld", (long long)rec0, (long long)(rec0 + nrec), (long long)v->nrecords); return MIH_BAD_DIM; }
     if (threads < 0) { set_error("threads must be >= 0"); return MIH_BAD_ARG; }
-    MIH_TRY(select_device(device));
+    return MIH_OK;
+}
+
+// Pass 2.  The tokeniser writes record r of the range into column r - rec0 of the u16 matrix Du (column stride ld), or -- pack
+// given -- into a panel of the worker's own that holds the chunk's records, which the pack kernel, queued behind it on the
+// worker's stream, turns into those columns of the builder's 2-bit image (a record that is no hard call: MIH_VCF_NOT_HARD_CALL).
+// *gcd_out: the gcd of 10^4 and every positive DS numerator.  The caller owns the target and drops it on any failure.
+static int vcf_stream(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int device, uint16_t *Du, int64_t ld,
+                      mih_snp_builder *pack, uint32_t *gcd_out, int64_t *bad_record, int32_t *bad_what)
+{
     v->meta.clear();
     const int64_t n = v->n, rec1 = rec0 + nrec;
     // the chunks that hold records of the range
@@ -737,20 +745,18 @@ int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int
     const int64_t desc_bytes = round_up((max_rec + 1) * (int64_t)sizeof(VcfRec), 256);
     unsigned nth = v->container == 1 ? 1u : default_workers(threads);    // a gzip stream has one reader
     if ((int64_t)nth > c_hi - c_lo) nth = (unsigned)(c_hi - c_lo);
+    const size_t panel_elems = pack ? (size_t)(max_rec * ld) : 0;         // one worker's panel: the records of the longest chunk
     const size_t staging_budget = 512ull << 20, per_worker = (size_t)(2 * (buf_bytes + desc_bytes));
-    if (per_worker * nth > staging_budget) nth = (unsigned)std::max<size_t>(1, staging_budget / per_worker);
-
-    mih_mat *h = new mih_mat();
-    auto fail = [&](int code) { mih_mat_destroy(h); return code; };
-    int rc = dosage_alloc(h, n, nrec, 1, device);
-    if (rc) return fail(rc);
+    const size_t per_worker_dev = per_worker + 2 * sizeof(uint16_t) * panel_elems;
+    if (per_worker_dev * nth > staging_budget) nth = (unsigned)std::max<size_t>(1, staging_budget / per_worker_dev);
+    int rc = MIH_OK;
     DevBuf<unsigned long long> bad;
     DevBuf<uint32_t> gcdv, segcnt;
-    if ((rc = bad.alloc(1)) || (rc = gcdv.alloc(1)) || (rc = segcnt.alloc((size_t)(2 * nth * max_seg)))) return fail(rc);
+    if ((rc = bad.alloc(1)) || (rc = gcdv.alloc(1)) || (rc = segcnt.alloc((size_t)(2 * nth * max_seg)))) return rc;
     const unsigned long long bad0 = ~0ull;
     const uint32_t g0 = 10000u;
     if (hipMemcpy(bad.p, &bad0, sizeof(bad0), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(gcdv.p, &g0, sizeof(g0), hipMemcpyHostToDevice) != hipSuccess) return fail(MIH_HIP_ERROR);
+        hipMemcpy(gcdv.p, &g0, sizeof(g0), hipMemcpyHostToDevice) != hipSuccess) return MIH_HIP_ERROR;
     struct Staging {
         uint8_t *pin = nullptr, *dev = nullptr;
         ~Staging() { if (pin) (void)hipHostFree(pin); if (dev) (void)hipFree(dev); }
@@ -761,9 +767,11 @@ int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int
         (void)hipGetLastError();
         if (stg.pin) { (void)hipHostFree(stg.pin); stg.pin = nullptr; }
         if (stg.dev) { (void)hipFree(stg.dev); stg.dev = nullptr; }
-        if (nth == 1) { set_error("allocation of the VCF staging buffers (%zu bytes pinned + device) failed", per_worker); return fail(MIH_OOM); }
+        if (nth == 1) { set_error("allocation of the VCF staging buffers (%zu bytes pinned + device) failed", per_worker); return MIH_OOM; }
         nth = 1;
     }
+    DevBuf<uint16_t> panels;
+    if (pack && (rc = panels.alloc(2 * nth * panel_elems))) return rc;
 
     std::atomic<unsigned long long> host_bad{~0ull};               // (record << 8) | reason, the least
     auto flag = [&](int64_t record, int what) {
@@ -810,6 +818,8 @@ int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int
             if (c < c_lo) { --it; continue; }                      // gzip: text before the range, inflated and dropped
             // ---- the records of the chunk: nine fields on the host, the rest described for the device
             int64_t rec = v->chunks[(size_t)c].rec0, nd = 0;
+            const int64_t rec_first = std::max(rec, rec0);          // a panel's column 0
+            const int64_t col_base = pack ? rec_first : rec0;
             uint32_t seg = 0;
             std::string &meta = metas[(size_t)c];
             for (int64_t p = 0; p < len;) {
@@ -841,7 +851,7 @@ int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int
                             if (!what && k < 0) what = MIH_VCF_NOKEY;
                         }
                         if (what) { flag(rec, what); break; }
-                        desc[nd++] = {(uint32_t)(16 + tab[8] + 1), (uint32_t)(16 + le), k, (int32_t)(rec - rec0), seg};
+                        desc[nd++] = {(uint32_t)(16 + tab[8] + 1), (uint32_t)(16 + le), k, (int32_t)(rec - col_base), seg};
                         const uint32_t a0 = (uint32_t)(16 + tab[8] + 1) & ~15u;
                         seg += std::max<uint32_t>(1u, (uint32_t)((16 + le - a0 + kVcfSeg - 1) / kVcfSeg));
                         meta.append((const char *)txt + p, (size_t)(tab[4] - p));
@@ -858,9 +868,13 @@ int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int
                 if (hipMemcpyAsync(dev, pin, (size_t)round_up(16 + len + 16, 16), hipMemcpyHostToDevice, r.st) != hipSuccess ||
                     hipMemcpyAsync(dev + buf_bytes, desc, (size_t)(nd + 1) * sizeof(VcfRec), hipMemcpyHostToDevice, r.st) != hipSuccess)
                     return broken("VCF worker: H2D copy");
-                hipLaunchKernelGGL(k_vcf_count, dim3(seg), dim3(256), 0, r.st, dev, ddesc, (int)nd, rec0, cnt, bad.p);
-                if (field) hipLaunchKernelGGL(k_vcf_parse<1>, dim3(seg), dim3(256), 0, r.st, dev, ddesc, (int)nd, rec0, cnt, n, h->Du, h->du_ld, bad.p, gcdv.p);
-                else hipLaunchKernelGGL(k_vcf_parse<0>, dim3(seg), dim3(256), 0, r.st, dev, ddesc, (int)nd, rec0, cnt, n, h->Du, h->du_ld, bad.p, gcdv.p);
+                uint16_t *dst = pack ? panels.p + (size_t)(2 * me + b) * panel_elems : Du;
+                hipLaunchKernelGGL(k_vcf_count, dim3(seg), dim3(256), 0, r.st, dev, ddesc, (int)nd, col_base, cnt, bad.p);
+                if (field) hipLaunchKernelGGL(k_vcf_parse<1>, dim3(seg), dim3(256), 0, r.st, dev, ddesc, (int)nd, col_base, cnt, n, dst, ld, bad.p, gcdv.p);
+                else hipLaunchKernelGGL(k_vcf_parse<0>, dim3(seg), dim3(256), 0, r.st, dev, ddesc, (int)nd, col_base, cnt, n, dst, ld, bad.p, gcdv.p);
+                // DS numerators are over 10^4 here (no gcd has been taken), GT counts over 1
+                if (pack && snp_builder_pack(pack, rec_first - rec0, nd, dst, ld, field ? 10000u : 1u, bad.p, (unsigned long long)rec_first, 8,
+                                             MIH_VCF_NOT_HARD_CALL, r.st) != MIH_OK) return broken("VCF worker: pack");
             }
             if (hipEventRecord(r.done[b], r.st) != hipSuccess) return broken("VCF worker: event record");
         }
@@ -872,26 +886,60 @@ int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int
         for (unsigned t = 0; t < nth; ++t) th.emplace_back(worker);
         for (auto &t : th) t.join();
     }
-    if (failed.load()) { set_error("%s", err_msg.c_str()); (void)hipGetLastError(); return fail(MIH_HIP_ERROR); }
+    if (failed.load()) { set_error("%s", err_msg.c_str()); (void)hipGetLastError(); return MIH_HIP_ERROR; }
 
     unsigned long long dev_bad = ~0ull;
     uint32_t g = 10000u;
     if (hipMemcpy(&dev_bad, bad.p, sizeof(dev_bad), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&g, gcdv.p, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess) return fail(MIH_HIP_ERROR);
+        hipMemcpy(&g, gcdv.p, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess) return MIH_HIP_ERROR;
     const unsigned long long first = std::min(dev_bad, host_bad.load());
     if (first != ~0ull) {
-        mih_mat_destroy(h);
         *bad_record = (int64_t)(first >> 8); *bad_what = (int32_t)(first & 0xFF);
         set_error("%s: record %lld: %s", v->path.c_str(), (long long)(*bad_record + 1), vcf_reason(*bad_what));
         return MIH_BAD_ARG;
     }
+    for (int64_t c = c_lo; c < c_hi; ++c) v->meta += metas[(size_t)c];
+    *gcd_out = g;
+    return MIH_OK;
+}
+
+int mih_dosage_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int device, mih_mat **out,
+                          int32_t *denom_out, int64_t *bad_record, int32_t *bad_what)
+{
+    if (!v || !out || !denom_out || !bad_record || !bad_what) { set_error("null argument"); return MIH_BAD_ARG; }
+    *out = nullptr; *bad_record = -1; *bad_what = 0;
+    MIH_TRY(vcf_check_args(v, field, rec0, nrec, threads));
+    MIH_TRY(select_device(device));
+    mih_mat *h = new mih_mat();
+    auto fail = [&](int code) { mih_mat_destroy(h); return code; };
+    int rc = dosage_alloc(h, v->n, nrec, 1, device);
+    if (rc) return fail(rc);
+    uint32_t g = 10000u;
+    if ((rc = vcf_stream(v, field, rec0, nrec, threads, device, h->Du, h->du_ld, nullptr, &g, bad_record, bad_what))) return fail(rc);
     if (field && g > 1u) hipLaunchKernelGGL(k_vcf_reduce, dim3((unsigned)h->p), dim3(256), 0, h->stream, h->Du, h->du_ld, g);
     h->denom = field ? (int32_t)(10000u / g) : 1;
     if ((rc = dosage_stats(h))) return fail(rc);
-    for (int64_t c = c_lo; c < c_hi; ++c) v->meta += metas[(size_t)c];
     *denom_out = h->denom;
     *out = h;
     return MIH_OK;
+}
+
+int mih_snp_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int center, int scale, int impute, int dtype,
+                       int device, mih_mat **out, int64_t *bad_record, int32_t *bad_what)
+{
+    if (!v || !out || !bad_record || !bad_what) { set_error("null argument"); return MIH_BAD_ARG; }
+    *out = nullptr; *bad_record = -1; *bad_what = 0;
+    MIH_TRY(vcf_check_args(v, field, rec0, nrec, threads));
+    mih_snp_builder *b = nullptr;
+    MIH_TRY(mih_snp_builder_create(v->n, nrec, center, scale, impute, dtype, device, &b));
+    uint32_t g = 10000u;
+    int rc = vcf_stream(v, field, rec0, nrec, threads, device, nullptr, round_up(v->n, 8), b, &g, bad_record, bad_what);
+    if (!rc) {
+        snp_builder_cover_all(b);
+        rc = mih_snp_builder_finish(b, out);
+    }
+    mih_snp_builder_destroy(b);
+    return rc;
 }
 
 }  // extern "C"

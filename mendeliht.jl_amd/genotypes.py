@@ -15,7 +15,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from .api import ArgumentError, DenseMatrix, DimensionMismatch, DosageMatrix, SnpLinAlg, _count_lines, _read_bim
+from .api import ArgumentError, DenseMatrix, DimensionMismatch, DosageMatrix, SnpBuilder, SnpLinAlg, _count_lines, _read_bim, _snp_dtype
 
 MAX_DENOM = 32767
 MISSING = 0xFFFF
@@ -425,6 +425,47 @@ def read_bgen_device(path, sample_path=None, variants=None, threads=None, device
     return x, idx.samples, idx.chrom[a:e], idx.pos[a:e], idx.ids[a:e], idx.ref[a:e], idx.alt[a:e]
 
 
+PANEL_BYTES = 1 << 30          # read_bgen_snp: u16 numerators held at a time
+
+
+def read_bgen_snp(path, sample_path=None, variants=None, panel=None, threads=None, device=0, center=True, scale=True, impute=True,
+                  dtype=np.float64, reserve=None):
+    """read_bgen_device's 7-tuple with a SnpLinAlg first, for a file of hard calls (every probability 0 or 1): the headers are
+    walked once, then panels of `panel` variants (default: about 1 GB of u16 numerators) are streamed into the device by
+    read_bgen_device, packed into the 2-bit image (SnpBuilder.add) and dropped, so device memory peaks at the 2-bit image plus
+    one panel.  The matrix is SnpLinAlg of the .bed encoding of the same genotypes, bit for bit.  A marker with a fractional
+    dosage raises an ArgumentError naming it; the other refusals are read_bgen_device's."""
+    path = str(path)
+    if variants is not None and (not isinstance(variants, range) or variants.step != 1):
+        raise ArgumentError("variants must be a contiguous range of 0-based variant indices")
+    idx = bgen_index(path, sample_path, variants)
+    a, e = (0, idx.nvariants) if variants is None else (variants.start, variants.stop)
+    if not 0 <= a <= e <= idx.nvariants:
+        raise ArgumentError(f"variants {variants} out of range for {idx.nvariants} variants")
+    if idx.nvariants == 0:
+        raise _NotStreamable(f"{path} holds no variants")
+    if a == e:
+        raise ArgumentError(f"variants {variants} is empty")
+    step = int(panel) if panel else max(1, PANEL_BYTES // (2 * ((idx.n + 7) // 8 * 8)))
+    if step < 1:
+        raise ArgumentError("panel must be a positive number of variants")
+    b = SnpBuilder(idx.n, e - a, center=center, scale=scale, impute=impute, dtype=dtype, device=device)
+    try:
+        for lo in range(a, e, step):
+            hi = min(lo + step, e)
+            part = read_bgen_device(path, sample_path, range(lo, hi), threads, device)[0]
+            try:
+                b.add(lo - a, part)
+            except ArgumentError:
+                raise ArgumentError(f"{path}: marker {a + b.bad_col + 1}: a dosage other than 0, 1 or 2: not a hard call") from None
+            finally:
+                del part
+        x = b.finish(reserve)
+    finally:
+        b.close()
+    return x, idx.samples, idx.chrom, idx.pos, idx.ids, idx.ref, idx.alt
+
+
 # ---- VCF, streamed -----------------------------------------------------------------------------
 def _vcf_text(fn, v):
     """The text a mih_vcf_header / mih_vcf_meta call holds, as bytes."""
@@ -445,6 +486,25 @@ def read_vcf_device(path, dosage=False, variants=None, threads=None, device=0, c
     this path does not take -- anything but GT alleles 0 1 . and plain decimals of at most 4 places up to 2, ragged or
     multi-allelic records, '\r', header or container trouble, a path that is no readable regular file -- raises _NotStreamable, naming the 1-based record and the reason:
     parse_genotypes reads such a file with read_vcf, whose results and errors stay what they are."""
+    return _read_vcf_streamed(path, dosage, variants, threads, device, chunk_bytes, None)
+
+
+def read_vcf_snp(path, dosage=False, variants=None, threads=None, device=0, chunk_bytes=None, center=True, scale=True, impute=True,
+                 dtype=np.float64, reserve=None):
+    """read_vcf_device's 7-tuple with a SnpLinAlg first, for a file of hard calls: GT, or DS (dosage=True) where every value is
+    0, 1 or 2.  The text is streamed as read_vcf_device streams it, but the tokeniser writes a small panel per chunk that is
+    packed at once into the 2-bit image (mih_snp_create_vcf): device memory never holds n x p numerators.  The matrix is
+    SnpLinAlg of the .bed encoding of read_vcf's genotypes (ALT counted as allele 2), bit for bit.  A DS record with another
+    value raises an ArgumentError naming the 1-based record; every other refusal is read_vcf_device's _NotStreamable."""
+    return _read_vcf_streamed(path, dosage, variants, threads, device, chunk_bytes,
+                              (bool(center), bool(scale), bool(impute), _snp_dtype(dtype), reserve))
+
+
+_VCF_NOT_HARD_CALL = 10
+
+
+def _read_vcf_streamed(path, dosage, variants, threads, device, chunk_bytes, snp):
+    """read_vcf_device (snp None) and read_vcf_snp (snp = center, scale, impute, dtype, reserve)."""
     import ctypes as C
 
     from .api import _check, lib
@@ -477,12 +537,25 @@ def read_vcf_device(path, dosage=False, variants=None, threads=None, device=0, c
         except UnicodeDecodeError:
             raise _NotStreamable(f"{path}: record 1: sample ids that are not ASCII: not streamed") from None
         h, den = C.c_void_p(None), C.c_int32(0)
-        rc = L.mih_dosage_create_vcf(v, 1 if dosage else 0, a, e - a, int(threads or 0), device, C.byref(h), C.byref(den),
-                                     C.byref(br), C.byref(bw))
+        if snp is None:
+            rc = L.mih_dosage_create_vcf(v, 1 if dosage else 0, a, e - a, int(threads or 0), device, C.byref(h), C.byref(den),
+                                         C.byref(br), C.byref(bw))
+        else:
+            center, scale, impute, dtype, reserve = snp
+            rc = L.mih_snp_create_vcf(v, 1 if dosage else 0, a, e - a, int(threads or 0), int(center), int(scale), int(impute),
+                                      32 if dtype is np.float32 else 64, device, C.byref(h), C.byref(br), C.byref(bw))
+        if rc != 0 and bw.value == _VCF_NOT_HARD_CALL:
+            buf = C.create_string_buffer(1024)
+            L.mih_last_error(buf, 1024)
+            raise ArgumentError(buf.value.decode(errors="replace"))
         if rc != 0 and bw.value:
             raise cannot()
         _check(rc)
-        x = DosageMatrix(None, den.value, device=device, _handle=h)
+        if snp is None:
+            x = DosageMatrix(None, den.value, device=device, _handle=h)
+        else:
+            x = SnpLinAlg(None, center=center, scale=scale, impute=impute, device=device, _handle=h, dtype=dtype)
+            x._reserve(reserve)
         rows = [ln.split("\t") for ln in _vcf_text(L.mih_vcf_meta, v).decode("ascii").split("\n")[:-1]]
     finally:
         L.mih_vcf_close(v)
@@ -491,12 +564,19 @@ def read_vcf_device(path, dosage=False, variants=None, threads=None, device=0, c
 
 
 # ---- parse_genotypes ---------------------------------------------------------------------------
-def parse_genotypes(tgtfile, dosage=False, device=0):
+def parse_genotypes(tgtfile, dosage=False, device=0, two_bit=False):
     """parse_genotypes(tgtfile, dosage) -- wrapper.jl:451-485: (X, sample_ids, chr, pos, snpid, ref, alt).  VCF (`.vcf`,
     `.vcf.gz`; GT allele counts, or DS with dosage=True) and BGEN (`.bgen`) give a DosageMatrix (or, on a grid finer than
     1/32767, a DenseMatrix of the standardized values); a binary PLINK trio (the path without .bed/.bim/.fam) gives
-    SnpLinAlg(center=true, scale=true, impute=true).  Either way X is the standardized matrix the reference fits."""
+    SnpLinAlg(center=true, scale=true, impute=true).  Either way X is the standardized matrix the reference fits.
+    two_bit=True: a VCF or BGEN file of hard calls gives that SnpLinAlg too (read_vcf_snp, read_bgen_snp) -- the same standardized
+    matrix at an eighth of the memory, on the 2-bit kernels; a file that is not all hard calls, or one the streamed readers do
+    not take, is an ArgumentError in the reader's words (never a silent DosageMatrix)."""
     tgt = str(tgtfile)
+    if two_bit and tgt.endswith((".vcf", ".vcf.gz")):
+        return read_vcf_snp(tgt, dosage, device=device)
+    if two_bit and tgt.endswith(".bgen"):
+        return read_bgen_snp(tgt, device=device)
     if tgt.endswith((".vcf", ".vcf.gz")):
         try:
             return read_vcf_device(tgt, dosage, device=device)

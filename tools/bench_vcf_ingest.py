@@ -11,6 +11,11 @@ reader it replaces.  One JSON line per file: GT and 3-decimal DS, each as BGZF a
 
     python tools/bench_vcf_ingest.py [--n 500000] [--p 1000] [--threads 8] [--dir /tmp/vcf_bench]
     python tools/bench_vcf_ingest.py --stream-only FILE [--dosage]    # one streamed ingest (for rocprofv3 --kernel-trace --stats)
+
+--two-bit: the streamed ingest is genotypes.read_vcf_snp (hard calls packed into the 2-bit SnpLinAlg) instead of read_vcf_device;
+the large files' lines then also carry the device memory the finished matrix holds and the most that was in use while it was
+being built (hipMemGetInfo, sampled every 10 ms by a thread), against n x p u16.  With --stream-only --pack N P it times
+DosageMatrix.to_snp() of the seeded synthetic N x P matrix over the denominator 1 (hard calls) instead (the pack kernel alone, for rocprofv3).
 """
 import argparse
 import json
@@ -123,17 +128,56 @@ def inflate_only(path, threads, reps):
     return statistics.median(opens), statistics.median(once), statistics.median(twice), total.value
 
 
-def child(path, dosage, threads, reps):
+class FreeMemory:
+    """free device memory as the HIP runtime of this process reports it; watch(): the least seen until stop()"""
+
+    def __init__(self):
+        import ctypes as C
+        path = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0]
+        self.hip, self.C = C.CDLL(path), C
+        self.low, self.on = None, False
+
+    def now(self):
+        f, t = self.C.c_size_t(0), self.C.c_size_t(0)
+        assert self.hip.hipMemGetInfo(self.C.byref(f), self.C.byref(t)) == 0
+        return f.value
+
+    def watch(self):
+        import threading
+        self.low, self.on = self.now(), True
+
+        def loop():
+            while self.on:
+                self.low = min(self.low, self.now())
+                time.sleep(0.01)
+        self.thread = threading.Thread(target=loop)
+        self.thread.start()
+
+    def stop(self):
+        self.on = False
+        self.thread.join()
+        return self.low
+
+
+def child(path, dosage, threads, reps, two_bit=False):
     import mendeliht_amd as m
     from mendeliht_amd import genotypes as G
     m.DosageMatrix(np.zeros((64, 2), np.uint16), 1).export()          # the runtime is up
     rss0 = kb("VmRSS")
-    walls = []
+    walls, mem = [], {}
     for _ in range(reps):
+        if two_bit:
+            free = FreeMemory()
+            before = free.now()
+            free.watch()
         t = time.perf_counter()
-        x = G.read_vcf_device(path, dosage, threads=threads)[0]
+        x = (G.read_vcf_snp if two_bit else G.read_vcf_device)(path, dosage, threads=threads)[0]
         walls.append(time.perf_counter() - t)
-        den, n, p = x.denom, x.n, x.p
+        den, n, p = getattr(x, "denom", 1), x.n, x.p
+        if two_bit:
+            low = free.stop()
+            mem = dict(two_bit=True, device_MB_held=round((before - free.now()) / 2 ** 20, 1), device_MB_peak=round((before - low) / 2 ** 20, 1),
+                       u16_MB=round(2 * n * p / 2 ** 20, 1))
         del x
     grow = (kb("VmHWM") - rss0) / 1024
     open_s, one, two, text = inflate_only(path, threads, reps)
@@ -141,7 +185,7 @@ def child(path, dosage, threads, reps):
     return dict(n=n, p=p, denom=den, threads=threads, stream_s=round(w, 3), stream_s_all=[round(v, 3) for v in walls],
                 records_per_s=round(p / w, 1), text_GB_s=round(text / w / 1e9, 3), text_MB=text >> 20, file_MB=os.path.getsize(path) >> 20,
                 peak_rss_growth_MB=round(grow, 1), scan_s=round(open_s, 3), inflate_once_s=round(one, 3), inflate_only_s=round(two, 3),
-                stream_over_inflate=round(w / two, 3))
+                stream_over_inflate=round(w / two, 3), **mem)
 
 
 def small(path, dosage):
@@ -174,15 +218,32 @@ def main():
     ap.add_argument("--child", nargs=2, metavar=("FILE", "MODE"))
     ap.add_argument("--stream-only", metavar="FILE")
     ap.add_argument("--dosage", action="store_true")
+    ap.add_argument("--two-bit", action="store_true")
+    ap.add_argument("--pack", nargs=2, type=int, metavar=("N", "P"))
     a = ap.parse_args()
+    if a.pack:
+        import mendeliht_amd as m
+        n, p = a.pack
+        d = m.DosageMatrix.synthetic(n, p, seed=5, denom=1, missing_rate=0.01)      # over the denominator 1 the generator emits hard calls
+        walls = []
+        for _ in range(a.reps):
+            t = time.perf_counter()
+            y = d.to_snp(reserve=False)
+            walls.append(time.perf_counter() - t)
+            if len(walls) < a.reps:
+                del y
+        bits = np.unpackbits(y.export_bed()[:3], axis=1, bitorder="little").reshape(3, -1, 2)[:, :n]
+        same = np.array_equal(np.array([0, 0xFFFF, 1, 2], dtype=np.uint16)[bits[:, :, 0] + 2 * bits[:, :, 1]].T, d.export(0, 3))
+        print(json.dumps(dict(n=n, p=p, to_snp_s=[round(v, 4) for v in walls], equals_source=bool(same))))
+        return
     if a.stream_only:
         from mendeliht_amd import genotypes as G
         t = time.perf_counter()
-        x = G.read_vcf_device(a.stream_only, a.dosage, threads=a.threads)[0]
-        print(json.dumps(dict(stream_s=round(time.perf_counter() - t, 3), p=x.p, denom=x.denom)))
+        x = (G.read_vcf_snp if a.two_bit else G.read_vcf_device)(a.stream_only, a.dosage, threads=a.threads)[0]
+        print(json.dumps(dict(stream_s=round(time.perf_counter() - t, 3), p=x.p, denom=getattr(x, "denom", 1), two_bit=a.two_bit)))
         return
     if a.child:
-        out = child(a.child[0], a.dosage, a.threads, a.reps) if a.child[1] == "stream" else small(a.child[0], a.dosage)
+        out = child(a.child[0], a.dosage, a.threads, a.reps, a.two_bit) if a.child[1] == "stream" else small(a.child[0], a.dosage)
         print(json.dumps(out))
         return
     os.makedirs(a.dir, exist_ok=True)
@@ -198,7 +259,7 @@ def main():
             jobs += [(tag, kind, base + f".{kind}.vcf.gz") for kind in (("bgzf", "gz1") if tag == "large" else ("bgzf",))]
         for tag, kind, path in jobs:
             cmd = [sys.executable, __file__, "--child", path, "stream" if tag == "large" else "small", "--threads", str(a.threads),
-                   "--reps", str(a.reps)] + (["--dosage"] if dosage else [])
+                   "--reps", str(a.reps)] + (["--dosage"] if dosage else []) + (["--two-bit"] if a.two_bit and tag == "large" else [])
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise SystemExit(r.stdout + r.stderr)
