@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf: additions, the version stays); 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -188,6 +188,27 @@ int mih_snp_create_dosage(const mih_mat *dosage, int center, int scale, int impu
  * MIH_VCF_NOT_HARD_CALL; every other refusal, and mih_vcf_meta afterwards, are mih_dosage_create_vcf's. */
 int mih_snp_create_vcf(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int threads, int center, int scale, int impute, int dtype,
                        int device, mih_mat **out, int64_t *bad_record, int32_t *bad_what);
+/* Quality control and sample selection on the device, for 2-bit handles (any other handle: MIH_BAD_ARG) -- what
+ * SnpArrays.filter(s; min_success_rate_per_row, min_success_rate_per_col, min_maf) and the selection of samples do before any
+ * fit_iht in manuscript/NFBC_sim/NFBC_data_qc.jl and manuscript/UKBB_metabolomic/data_process.jl, and what SnpArrays.maf gives
+ * src/utilities.jl:687-693 -- without the matrix leaving the device.
+ *
+ * mih_snp_counts: the genotype counts of every kept column over the kept rows, and the missing genotypes of every kept row
+ * among the kept columns.  row_keep (n bytes) and col_keep (p bytes) are 0 / 1 masks in host memory, NULL = everything;
+ * col_counts (4 p, may be NULL) receives n0, n1, n2, nmiss of column j in col_counts[4 j ..], zeros for a column that is not
+ * kept; row_missing (n, may be NULL) receives 0 for a row that is not kept.  All integers, so exact.  n1 and n2 are masked
+ * population counts in one pass over the tiles, nmiss and row_missing come from the missing lists alone, n0 is the rest:
+ * with col_counts == NULL the tiles are not read. */
+int mih_snp_counts(const mih_mat *h, const uint8_t *row_keep, const uint8_t *col_keep, int32_t *col_counts, int32_t *row_missing);
+/* mih_snp_subset: rows `rows` and columns `cols` of a 2-bit matrix as a new, ordinary, immutable handle on the same device --
+ * bit for bit the handle mih_snp_create builds from the .bed codes of the selected genotypes (image, mu and sinv over the kept
+ * rows, missing lists), which a `train` mask of a fit is not: mu and sinv of a matrix are taken over all of its rows.  rows
+ * (nrows entries) and cols (ncols entries) are strictly increasing 0-based indices in host memory, NULL = all.  The source is
+ * only read and stays usable; beyond source and result the device holds O(n + p) bytes, and no genotype crosses the host link.
+ * center, scale, impute, dtype and the reserve rule: as mih_snp_create.  Refusals (MIH_BAD_ARG, nothing allocated): a handle
+ * that is not 2-bit, an empty selection, an index out of range, indices that are not strictly increasing. */
+int mih_snp_subset(const mih_mat *h, const int64_t *rows, int64_t nrows, const int64_t *cols, int64_t ncols,
+                   int center, int scale, int impute, int dtype, mih_mat **out);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import sys
 import time
+import warnings
 
 import numpy as np
 
@@ -171,6 +172,8 @@ def lib():
         "mih_mat_reserve": [vp, i64],
         "mih_snp_mu_sigma": [vp, vp, vp],
         "mih_snp_export_bed": [vp, vp],
+        "mih_snp_counts": [vp, vp, vp, vp, vp],
+        "mih_snp_subset": [vp, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -227,7 +230,7 @@ def exported_symbols():
             "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -503,6 +506,109 @@ class SnpLinAlg(_Mat):
         out = np.empty((self.p, (self.n + 3) // 4), dtype=np.uint8)
         _check(lib().mih_snp_export_bed(self._h, _p(out)))
         return out
+
+    # ---- quality control and sample selection on the device (csrc/qc.hip) ----
+    @staticmethod
+    def _sel_indices(sel, length, what):
+        """A boolean mask or an index array as int64 indices (None: everything).  The order and range of an index array are
+        left to whoever takes it."""
+        if sel is None:
+            return None
+        sel = np.asarray(sel)
+        if sel.dtype == np.bool_:
+            if sel.shape != (length,):
+                raise DimensionMismatch(f"the {what} mask has shape {sel.shape}, expected ({length},)")
+            return np.flatnonzero(sel).astype(np.int64)
+        if sel.ndim != 1 or not (np.issubdtype(sel.dtype, np.integer) or sel.size == 0):
+            raise ArgumentError(f"the {what} selection must be a boolean mask or a one-dimensional array of indices")
+        return np.ascontiguousarray(sel, dtype=np.int64)
+
+    @classmethod
+    def _sel_mask(cls, sel, length, what):
+        """The same selection as a byte mask for mih_snp_counts (None: everything)."""
+        idx = cls._sel_indices(sel, length, what)
+        if idx is None:
+            return None
+        if idx.size and (idx.min() < 0 or idx.max() >= length):
+            raise ArgumentError(f"a {what} index is outside 0 .. {length - 1}")
+        if np.any(np.diff(idx) <= 0):
+            raise ArgumentError(f"the {what} indices must be strictly increasing")
+        mask = np.zeros(length, dtype=np.uint8)
+        mask[idx] = 1
+        return mask
+
+    def counts(self, rows=None, cols=None):
+        """(col_counts (p, 4) int32: n0, n1, n2, nmiss of every kept column over the kept rows, zeros for a column that is not
+        kept; row_missing (n,) int32: the missing genotypes of every kept row among the kept columns, 0 for a row that is not
+        kept).  rows, cols: boolean masks or strictly increasing index arrays, None = all.  Counted on the device
+        (mih_snp_counts); the integers are exact."""
+        rk, ck = self._sel_mask(rows, self.n, "row"), self._sel_mask(cols, self.p, "column")
+        col_counts, row_missing = np.empty((self.p, 4), dtype=np.int32), np.empty(self.n, dtype=np.int32)
+        _check(lib().mih_snp_counts(self._h, _p(rk), _p(ck), _p(col_counts), _p(row_missing)))
+        return col_counts, row_missing
+
+    def maf(self, rows=None):
+        """SnpArrays.maf over the kept rows: min(f, 1 - f) with f the frequency of allele 2 among the non-missing genotypes
+        (NaN for a column with none)."""
+        return _maf_of(self.counts(rows=rows)[0])
+
+    def missing_rate(self, axis):
+        """The share of missing genotypes per column (axis = 0: over the rows, length p) or per row (axis = 1, length n)."""
+        if axis not in (0, 1):
+            raise ArgumentError("axis must be 0 (per column) or 1 (per row)")
+        if axis == 0:
+            return self.counts()[0][:, 3] / float(self.n)
+        row_missing = np.empty(self.n, dtype=np.int32)
+        _check(lib().mih_snp_counts(self._h, None, None, None, _p(row_missing)))      # from the missing lists alone
+        return row_missing / float(self.p)
+
+    def subset(self, rows=None, cols=None, center=None, scale=None, impute=None, dtype=None, reserve=None):
+        """x[rows, cols] as a new SnpLinAlg, made on the device (mih_snp_subset): bit for bit the SnpLinAlg of the .bed encoding
+        of the selected genotypes, with mu and 1/sigma over the kept rows.  rows, cols: boolean masks or strictly increasing
+        index arrays, None = all; the flags default to this matrix's; reserve as in the constructor.  This matrix is unchanged."""
+        center = self.center if center is None else bool(center)
+        scale = self.scale if scale is None else bool(scale)
+        impute = self.impute if impute is None else bool(impute)
+        dtype = self.dtype if dtype is None else _snp_dtype(dtype)
+        ridx, cidx = self._sel_indices(rows, self.n, "row"), self._sel_indices(cols, self.p, "column")
+        for what, idx in (("rows", ridx), ("columns", cidx)):
+            if idx is not None and idx.size == 0:              # (an empty array has no address to hand over)
+                raise ArgumentError(f"the selection of {what} is empty")
+        h = C.c_void_p(None)
+        _check(lib().mih_snp_subset(self._h, _p(ridx), 0 if ridx is None else ridx.size, _p(cidx), 0 if cidx is None else cidx.size,
+                                    int(center), int(scale), int(impute), 32 if dtype is np.float32 else 64, C.byref(h)))
+        x = SnpLinAlg(None, center=center, scale=scale, impute=impute, device=self.device, _handle=h, dtype=dtype)
+        x._reserve(reserve)
+        return x
+
+    def filter(self, min_success_rate_per_row=0.98, min_success_rate_per_col=0.98, min_maf=0.01, maxiters=5):
+        """SnpArrays.filter (without the Hardy-Weinberg test): boolean masks (rmask, cmask) of the rows and columns that are left
+        when rows and columns below the success rates, and columns below min_maf, are dropped in turn until nothing changes or
+        maxiters rounds have run (then a warning).  Each round counts on the device under the current masks (mih_snp_counts),
+        both counts before either mask changes; the thresholds are applied on the host in float64."""
+        rmask, cmask = np.ones(self.n, dtype=np.bool_), np.ones(self.p, dtype=np.bool_)
+        rmiss, cmiss = 1.0 - float(min_success_rate_per_row), 1.0 - float(min_success_rate_per_col)
+        for _ in range(int(maxiters)):
+            col_counts, row_missing = self.counts(rmask, cmask)
+            rows, cols = int(np.count_nonzero(rmask)), int(np.count_nonzero(cmask))
+            ckeep = cmask & (col_counts[:, 3] < cmiss * rows)
+            if min_maf > 0:
+                with np.errstate(invalid="ignore"):
+                    ckeep &= _maf_of(col_counts) >= min_maf                    # (NaN fails)
+            rkeep = rmask & (row_missing < rmiss * cols)
+            changed = int(np.count_nonzero(rkeep)) != rows or int(np.count_nonzero(ckeep)) != cols
+            rmask, cmask = rkeep, ckeep
+            if not changed:
+                return rmask, cmask
+        warnings.warn(f"filter: maxiters = {maxiters} reached, the success rates may not be satisfied", stacklevel=2)
+        return rmask, cmask
+
+
+def _maf_of(col_counts):
+    n0, n1, n2 = (col_counts[:, k].astype(np.float64) for k in range(3))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = (n1 + 2.0 * n2) / (2.0 * (n0 + n1 + n2))
+    return np.minimum(f, 1.0 - f)
 
 
 def _snp_dtype(dtype):

@@ -363,6 +363,15 @@ __device__ __forceinline__ double dosage_x(const DosageView &v, int64_t j, int64
 int snp_builder_pack(mih_snp_builder *b, int64_t col0, int64_t ncols, const uint16_t *panel, int64_t ld, uint32_t unit,
                      unsigned long long *bad, unsigned long long bad_base, int bad_shift, unsigned long long bad_low, hipStream_t s);
 void snp_builder_cover_all(mih_snp_builder *b);
+// snp.hip: what every constructor of a 2-bit matrix shares (qc.hip builds one matrix from another).  alloc_snp: the image (left
+// uncleared), mu and sinv for h->n x h->p; finish_counts: mu, sinv, the missing lists' offsets and room for their rows from the
+// per-column counters cnt[3 j + {n1, n2, nmiss}]; finish_tiles: that, and the lists' rows from an image whose missing entries
+// carry the temporary code 3 (which it turns into code 0); reserve_fit_memory: the reserve rule of mih_snp_create (asked:
+// whatever the size, asked_bytes = 0: sized by the rule).
+int alloc_snp(mih_mat *h);
+int finish_counts(mih_mat *h, const int32_t *cnt_dev);
+int finish_tiles(mih_mat *h, const int32_t *cnt_dev);
+void reserve_fit_memory(mih_mat *h, bool asked = false, size_t asked_bytes = 0);
 constexpr int kWorkerStreamsPerLane = 4;       // the runtime maps streams onto a handful of hardware queues anyway
 // stream i of the matrix's worker set (i < 2 * kWorkerStreamsPerLane); nullptr if it cannot be created
 hipStream_t worker_stream(const mih_mat *h, int i);

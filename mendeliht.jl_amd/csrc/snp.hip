@@ -385,24 +385,30 @@ static int finish_missing_ptr(mih_mat *h, const std::vector<int32_t> &cnt, std::
     return MIH_OK;
 }
 
-// What follows the last transcode (or pack) of a matrix: mu and sinv from the per-column counts, the missing lists, and the
-// tiles' temporary code 3 turned into dosage 0.
-static int finish_tiles(mih_mat *h, const int32_t *cnt_dev)
+// mu and sinv from the per-column counts cnt[3 j + {n1, n2, nmiss}], and the missing lists' offsets with room for the rows.
+int finish_counts(mih_mat *h, const int32_t *cnt_dev)
 {
     const int64_t p = h->p;
     hipLaunchKernelGGL(k_col_stats, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, h->stream, cnt_dev, h->n, p, h->mu, h->sinv);
     std::vector<int32_t> hcnt((size_t)(3 * p));
     if (hipMemcpy(hcnt.data(), cnt_dev, sizeof(int32_t) * hcnt.size(), hipMemcpyDeviceToHost) != hipSuccess) return MIH_HIP_ERROR;
     std::vector<int64_t> ptr;
-    MIH_TRY(finish_missing_ptr(h, hcnt, ptr));
+    return finish_missing_ptr(h, hcnt, ptr);
+}
+
+// What follows the last transcode (or pack) of a matrix: mu and sinv from the per-column counts, the missing lists, and the
+// tiles' temporary code 3 turned into dosage 0.
+int finish_tiles(mih_mat *h, const int32_t *cnt_dev)
+{
+    MIH_TRY(finish_counts(h, cnt_dev));
     if (h->total_missing > 0)
-        hipLaunchKernelGGL(k_missing_from_tiles, dim3((unsigned)h->ncg), dim3(64), 0, h->stream, reinterpret_cast<uint4 *>(h->X), h->nbp, p,
+        hipLaunchKernelGGL(k_missing_from_tiles, dim3((unsigned)h->ncg), dim3(64), 0, h->stream, reinterpret_cast<uint4 *>(h->X), h->nbp, h->p,
                            h->miss_ptr, h->miss_row);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return MIH_HIP_ERROR;
     return MIH_OK;
 }
 
-static int alloc_snp(mih_mat *h)
+int alloc_snp(mih_mat *h)
 {
     h->ncg = (h->p + 31) / 32;
     h->nbp = (h->n + 127) / 128;
@@ -510,7 +516,7 @@ int mih_last_error(char *buf, size_t len)
 int mih_version(int *major, int *minor)
 {
     if (major) *major = 0;
-    if (minor) *minor = 7;        // 0.7: mih_vcf_*, mih_dosage_create_vcf (and, added without a bump, mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf); 0.6: mih_dosage_create_bgen, mih_dosage_regrid; 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
+    if (minor) *minor = 7;        // 0.7: mih_vcf_*, mih_dosage_create_vcf (and, added without a bump, mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf, mih_snp_counts, mih_snp_subset); 0.6: mih_dosage_create_bgen, mih_dosage_regrid; 0.5: mih_dosage_create*, mih_dosage_export; round 4: mih_fit_params::cv_threads, mih_cv_allgather, MIH_CNT_INIT_SCORES; round 3: mih_fit_params::xtv_digits, mih_xtv_batched_fmt, mih_profile_* per handle, mih_cv_assignment; mih_set_* gone
     return MIH_OK;
 }
 
@@ -523,6 +529,8 @@ int mih_abi_sizes(int64_t *sizes, int32_t n)
     return MIH_OK;
 }
 
+}  // extern "C"
+
 // A large matrix reserves the device memory its fits will work in (DevPool, common.h): about what a cross-validation asks for
 // -- four fused-pass workspaces and 64 IHTVariable blocks, 15.7 GB beside a 125 GB matrix.  Whatever the driver has to do to
 // hand out never-used VRAM (one stall of ~2.9 s was measured) it does here, when the matrix is created, and no fit ever calls
@@ -531,7 +539,7 @@ int mih_abi_sizes(int64_t *sizes, int32_t n)
 // (bytes = 0: sized by the rule below from its dimensions -- the test suite asks for it on its small matrices so that the pool,
 // the arenas and the lock-step hand-over run exactly as beside a 125 GB matrix) or takes it away (bytes < 0).
 // MENDELIHT_NO_RESERVE=1 is an A/B switch of the measurement build.
-static void reserve_fit_memory(mih_mat *h, bool asked = false, size_t asked_bytes = 0)
+void mih::reserve_fit_memory(mih_mat *h, bool asked, size_t asked_bytes)
 {
     static const bool off = probe_env("MENDELIHT_NO_RESERVE") != nullptr;
     const size_t min_bytes = (size_t)(4ull << 30);
@@ -551,6 +559,7 @@ static void reserve_fit_memory(mih_mat *h, bool asked = false, size_t asked_byte
     std::shared_ptr<DevPool> pool(new DevPool());
     if (pool->init(want)) { h->pool_owner = pool; h->pool = pool.get(); }
 }
+extern "C" {
 
 int mih_snp_create(const uint8_t *bed_cols, int64_t n, int64_t p, int64_t col_stride_bytes,
                    int center, int scale, int impute, int dtype, int device, mih_mat **out)
