@@ -29,7 +29,7 @@ int mih_probe_set_max_fused(int max_nr);
 /* X'r of the first ms[i] columns of R (n x mcap, column-major) for i = 0 .. nms-1, one call after the other on ONE fused-pass
  * workspace sized for mcap residuals -- what a lock-step lane does from round to round.  OUT: the results back to back
  * (p * ms[0] doubles, then p * ms[1], ...).  For the test that a pass ignores what an earlier pass with another residual
- * count left in the unused digit columns of its last operand (flat packing, csrc/xtv.hip). */
+ * count left in the unused digit columns of its last operand (flat packing: plan_passes in csrc/xtv.hip, xtv_epilogue16_flat in csrc/xtv_kernels.h). */
 int mih_probe_xtv_sequence(const mih_mat *h, const double *R, int mcap, const int *ms, int nms, int digits, double *OUT);
 /* X beta over a small support, ncalls products one after the other on ONE workspace (xv_work_init(h, w, max_nnz, cache_nnz):
  * its LRU column cache, its coefficient buffers) with ONE pinned upload ring sized as a fit sizes it -- the paths a fit takes

@@ -21,6 +21,8 @@ namespace mih {
 
 void set_error(const char *fmt, ...);
 int  hip_fail(hipError_t e, const char *what, const char *file, int line);
+// a function one translation unit calls in another and nobody outside the library: kept out of the dynamic symbol table
+#define MIH_LOCAL __attribute__((visibility("hidden")))
 
 // A/B switches and tuning knobs of the MEASUREMENT build (-DMIH_PROBES: libmendeliht_hip_probes.so, used by tools/ and by the
 // "this switch changes nothing" tests).  The release library does not read them: its behaviour is fixed by its arguments.
@@ -293,6 +295,9 @@ struct Profile {
     void drain();                                // synchronise the open records into `done`
     ~Profile();
 };
+// profile.hip: bracket one launch of the dominant kernel; prof_begin says whether the hook is on (then prof_end files the record)
+MIH_LOCAL bool prof_begin(const ::mih_mat *h, hipStream_t s, PassRecord &rec);
+MIH_LOCAL void prof_end(const ::mih_mat *h, hipStream_t s, PassRecord &rec);
 }  // namespace mih
 
 // Device-resident design matrix.
@@ -445,7 +450,7 @@ struct XtvStatsHook {
     const double *zpart = nullptr; double *df2 = nullptr; int q = 0, zblocks = 0;
     int ebits = 0;
 };
-// walk-blocks per residual of the statistics of r (max |r|, sum r): k_r_stats (xtv.hip) and k_res_stats (resident.inc)
+// walk-blocks per residual of the statistics of r (max |r|, sum r): k_r_stats (xtv_digits.hip) and k_res_stats (resident.inc)
 // form the same partial sums in the same order, and the digit kernel finishes either's
 constexpr int kStatBlocks = 64;
 struct XtvWork {            // scratch for one in-flight X'r
@@ -476,6 +481,13 @@ int  xtv_device(const mih_mat *h, XtvWork &w, const double *r_dev, int m, double
 void xtv_count_peels(const mih_mat *h, XtvWork &w, hipStream_t s);
 // residuals of two full fused passes (six operands each by default) in the batched format: how many fits the lock-step drivers keep in flight
 int  xtv_lockstep_width(const mih_mat *h, const XtvTune &tune);
+// xtv_digits.hip: k_r_stats over m residuals; k_digits over `slots` residual slots (grid rows)
+MIH_LOCAL void launch_r_stats(const double *r_dev, int64_t n, int m, double *part, unsigned *done, int ebits, double *scal,
+                    const int32_t *gate, int32_t gate_val, double *peel, hipStream_t s);
+MIH_LOCAL void launch_digits(const double *r_dev, int64_t n, int64_t nblk, int m, int slots, const DigitMode &dm, double *scal, uint4 *dig, uint2 *dig2,
+                   const FlatPasses &fp, const XtvStatsHook &sh, const double *peel, hipStream_t s);
+// xtv_dense.hip: the pass over a dense f64 / f32 matrix or the 16-bit dosage image (h->kind == 1)
+MIH_LOCAL int xtv_dense_device(const mih_mat *h, const XtvWork &w, const double *r_dev, int m, double *out_dev, hipStream_t s);
 
 // ---- X[:,S] v -----------------------------------------------------------------
 struct XvWork {

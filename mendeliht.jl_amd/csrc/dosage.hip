@@ -2,7 +2,7 @@
 // num / denom, stored as u16 numerators (4x less HBM than the reference's Matrix{Float64}).  Ingest, the column statistics of
 // standardize_genotypes! (src/wrapper.jl:406-423), the seeded synthetic generator and the export of numerators.  The matrix
 // is a dense one (kind 1) to every fit; the sites that read its storage standardize per entry (common.h: dosage_x,
-// xtv.hip: k_xtv_dosage_lds).
+// xtv_dense.hip: k_xtv_dosage_lds).
 #include "common.h"
 #include <cmath>
 

@@ -1,6 +1,6 @@
 // peel.h -- the outlier side channel of the fixed-point residual (round 6).
 //
-// X'r runs in fixed point: r is scaled by a power of two so that max|r| fills 54 bits (xtv.hip), every entry is rounded to
+// X'r runs in fixed point: r is scaled by a power of two so that max|r| fills 54 bits (xtv.hip, xtv_digits.hip), every entry is rounded to
 // that quantum.  The reference's mul!(df, Transpose(x), r) (src/utilities.jl:133) is a floating-point dot product, so an entry
 // r_i keeps its own 53 bits there whatever the largest entry is; here it kept 54 + log2(|r_i| / max|r|) -- with ONE entry 1e8 x
 // the rest (a Poisson count the model has not caught up with, an unclamped GLM weight) the columns that do not carry that row

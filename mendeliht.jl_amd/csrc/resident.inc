@@ -32,7 +32,7 @@
 //   update_xb!, update_mu!, loglikelihood (:93-118,74-82,9-20)  k_res_xb (+ k_res_mu)
 //   _iht_backtrack_ / backtrack! (:484-486, 959-973)         k_res_decide (decision); the next attempt slot in the stream goes on
 //   score! residual (:128-132)                               k_res_xb / k_res_mu (the candidate's, from the values at hand)
-//   Z'r, the statistics of r (:134)                          k_res_stats (+ the second stages in k_digits); X'r = the gated pass of xtv.hip
+//   Z'r, the statistics of r (:134)                          k_res_stats (+ the second stages in k_digits); X'r = the gated pass of xtv.hip (k_digits: xtv_digits.hip)
 //   save_prev! / check_convergence (:702-712, 953-957)       buffer flip in k_res_decide, best model in k_res_xgk, tol in k_res_select
 // Serial tails (the second-stage sums with the step size, the decision) are one-workgroup kernels of their own, 2.5 us apiece;
 // NO counter is shared by a whole grid: a last-block ticket over 1954 blocks cost 100 us (measured: same-address atomics at ~60 ns

@@ -1,6 +1,6 @@
-// xtv_probes.inc -- MEASUREMENT BUILD ONLY (-DMIH_PROBES, libmendeliht_hip_probes.so; included by xtv.hip inside namespace mih).
-// Launch-shape sweeps of the ring kernels, the round-1 kernel families (register-staged k_xtv_mfma_lds, per-wave k_xtv_mfma)
-// kept as bit-for-bit cross-checks, and timing probes whose output is NOT X'r.  None of this is in libmendeliht_hip.so.
+// xtv_probes.inc -- MEASUREMENT BUILD ONLY (-DMIH_PROBES, libmendeliht_hip_probes.so; included by xtv.hip inside namespace mih, behind xtv_kernels.h).
+// Launch-shape sweeps of the ring kernels, the round-1 kernel families (register-staged k_xtv_mfma_lds; per-wave k_xtv_mfma, whose
+// text lives here) kept as bit-for-bit cross-checks, and timing probes whose output is NOT X'r.  None of this is in libmendeliht_hip.so.
 // The knobs are process-wide here on purpose: tools/ set them once per measurement (mih_probe_*), nothing else uses this library
 // concurrently.
 struct ProbeKnobs { int variant = -1, multi_variant = 0, max_nr = 4; };
@@ -40,6 +40,68 @@ constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 static int probe_splits(const XtvTune &tn) { return tn.variant >= 0 && tn.variant < kNumVariants ? kVariants[tn.variant].splits : 0; }
 
+// NR right-hand sides ride the same pass: the dosage tile is loaded and expanded once and fed to NR
+// MFMAs (one per residual vector's digit planes).
+template <int WAVES, int CT, int NR>
+__global__ void __launch_bounds__(WAVES * 64)
+k_xtv_mfma(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg, const uint4 *__restrict__ dig, int64_t dig_stride,
+           int splits, DigitMode dm, const double *__restrict__ scal, double *__restrict__ partial /* [NR*per_op][splits][ncg*32] */)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int split = blockIdx.x % splits;
+    const int64_t grp = blockIdx.x / splits;
+    const int64_t cg0 = (grp * WAVES + wave) * CT;
+    if (cg0 >= ncg) return;
+    const int64_t bps = (nbp + splits - 1) / splits;
+    const int64_t b0 = split * bps;
+    const int64_t b1 = (b0 + bps < nbp) ? b0 + bps : nbp;
+
+    f32x16 acc[CT][NR];
+    #pragma unroll
+    for (int c = 0; c < CT; ++c)
+        #pragma unroll
+        for (int v = 0; v < NR; ++v)
+            #pragma unroll
+            for (int g = 0; g < 16; ++g) acc[c][v][g] = 0.f;
+
+    if (b0 < b1) {
+        const uint4 *ap[CT];
+        #pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            int64_t cg = cg0 + c < ncg ? cg0 + c : ncg - 1;
+            ap[c] = X + (cg * nbp) * 64 + lane;
+        }
+        const uint4 *bp_ = dig + lane;
+        uint4 acur[CT], anext[CT], bcur[NR][2], bnext[NR][2];
+        #pragma unroll
+        for (int c = 0; c < CT; ++c) acur[c] = ld_stream(ap[c] + b0 * 64);
+        #pragma unroll
+        for (int v = 0; v < NR; ++v) { bcur[v][0] = bp_[v * dig_stride + (2 * b0) * 64]; bcur[v][1] = bp_[v * dig_stride + (2 * b0 + 1) * 64]; }
+        for (int64_t bp = b0; bp < b1; ++bp) {
+            const int64_t bn = (bp + 1 < b1) ? bp + 1 : bp;
+            #pragma unroll
+            for (int c = 0; c < CT; ++c) anext[c] = ld_stream(ap[c] + bn * 64);
+            #pragma unroll
+            for (int v = 0; v < NR; ++v) { bnext[v][0] = bp_[v * dig_stride + (2 * bn) * 64]; bnext[v][1] = bp_[v * dig_stride + (2 * bn + 1) * 64]; }
+            #pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                #pragma unroll
+                for (int v = 0; v < NR; ++v) {
+                    acc[c][v] = mfma_fp4(acur[c].x, acur[c].y, bcur[v][0], acc[c][v]);
+                    acc[c][v] = mfma_fp4(acur[c].z, acur[c].w, bcur[v][1], acc[c][v]);
+                }
+            }
+            #pragma unroll
+            for (int c = 0; c < CT; ++c) acur[c] = anext[c];
+            #pragma unroll
+            for (int v = 0; v < NR; ++v) { bcur[v][0] = bnext[v][0]; bcur[v][1] = bnext[v][1]; }
+        }
+    }
+
+    xtv_epilogue<CT, NR>(acc, lane, cg0, ncg, split, splits, dm, scal, partial);
+}
+
 template <int WAVES, int CT, int NR>
 static void launch_xtv(const mih_mat *h, const uint4 *dig, int64_t dig_stride, int splits, DigitMode dm, const double *scal,
                        double *partial, hipStream_t s)
@@ -56,24 +118,12 @@ static int dispatch_probe(const XtvTune &tn, int nr, bool half, const mih_mat *h
     const int mv6 = tn.multi_variant;
     if (mv6 == 0 && tn.variant < 0) return -1;
     (void)half;
-#define MIH_LDS6(NRV, ID, C, RB, W) if (nr == NRV && (mv6 == ID || ID < 0)) { \
-        int64_t groups = (h->ncg + W * C - 1) / (W * C); \
-        hipLaunchKernelGGL((k_xtv_mfma_lds<NRV, C, RB, 0, W, true>), dim3((unsigned)(groups * splits)), dim3(W * 64), 0, s, \
-                           reinterpret_cast<const uint4 *>(h->X), h->nbp, h->ncg, dig, dig2, dig_stride, splits, dm, scal, partial); \
-        snprintf(name, 48, "k_xtv_mfma_lds<%d,%d,%d,%d,fp6>", NRV, C, RB, W); \
-        return MIH_OK; }
-#define MIH_DMA(NRV, ID, C, W, DD, F6, MODE) if (nr == NRV && (mv6 == ID || ID < 0)) { \
-        int64_t groups = (h->ncg + W * C - 1) / (W * C); \
-        hipLaunchKernelGGL((k_xtv_dma<NRV, C, W, DD, F6, MODE>), dim3((unsigned)(groups * splits)), dim3(W * 64), 0, s, \
-                           reinterpret_cast<const uint4 *>(h->X), h->nbp, h->ncg, dig, dig2, dig_stride, splits, dm, scal, partial); \
-        snprintf(name, 48, "k_xtv_dma<%d,%d,%d,%d,%s%s>", NRV, C, W, DD, F6 ? "fp6" : "fp4", MODE ? ",probe" : ""); \
-        return MIH_OK; }
-#define MIH_DMA16M(NRV, ID, C, W, DD, MODE) if (nr == NRV && mv6 == ID) { \
-        int64_t groups = (h->ncg + W * C - 1) / (W * C); \
-        hipLaunchKernelGGL((k_xtv_dma16<NRV, C, W, DD, MODE, 0>), dim3((unsigned)(groups * splits)), dim3(W * 64), 0, s, \
-                           reinterpret_cast<const uint4 *>(h->X), h->nbp, h->ncg, dig, dig2, dig_stride, splits, dm, scal, partial); \
-        snprintf(name, 48, "k_xtv_dma16<%d,%d,%d,%d%s>", NRV, C, W, DD, MODE ? ",probe" : ""); \
-        return MIH_OK; }
+#define MIH_LDS6(NRV, ID, C, RB, W) if (nr == NRV && (mv6 == ID || ID < 0)) \
+        MIH_LAUNCH((k_xtv_mfma_lds<NRV, C, RB, 0, W, true>), W, C, "k_xtv_mfma_lds<%d,%d,%d,%d,fp6>", NRV, C, RB, W)
+#define MIH_DMA(NRV, ID, C, W, DD, F6, MODE) if (nr == NRV && (mv6 == ID || ID < 0)) \
+        MIH_LAUNCH((k_xtv_dma<NRV, C, W, DD, F6, MODE>), W, C, "k_xtv_dma<%d,%d,%d,%d,%s%s>", NRV, C, W, DD, F6 ? "fp6" : "fp4", MODE ? ",probe" : "")
+#define MIH_DMA16M(NRV, ID, C, W, DD, MODE) if (nr == NRV && mv6 == ID) \
+        MIH_LAUNCH((k_xtv_dma16<NRV, C, W, DD, MODE, 0>), W, C, "k_xtv_dma16<%d,%d,%d,%d%s>", NRV, C, W, DD, MODE ? ",probe" : "")
     if (dm.base == 49 && dm.lay16) {      // ids 40..49: other shapes of the 16x16x128 ring kernel; everything else: release defaults
         MIH_DMA16M(4, 40, 4, 4, 4, 0) MIH_DMA16M(3, 40, 4, 4, 4, 0) MIH_DMA16M(2, 40, 4, 4, 4, 0) MIH_DMA16M(1, 40, 4, 4, 4, 0)
         MIH_DMA16M(4, 42, 2, 8, 3, 0) MIH_DMA16M(4, 43, 2, 8, 2, 0)
@@ -102,12 +152,8 @@ static int dispatch_probe(const XtvTune &tn, int nr, bool half, const mih_mat *h
         return MIH_BAD_ARG;
     }
 #undef MIH_LDS6
-#define MIH_LDS(NRV, ID, C, RB, MODE, W) if (nr == NRV && mv6 == ID) { \
-        int64_t groups = (h->ncg + W * C - 1) / (W * C); \
-        hipLaunchKernelGGL((k_xtv_mfma_lds<NRV, C, RB, MODE, W>), dim3((unsigned)(groups * splits)), dim3(W * 64), 0, s, \
-                           reinterpret_cast<const uint4 *>(h->X), h->nbp, h->ncg, dig, dig2, dig_stride, splits, dm, scal, partial); \
-        snprintf(name, 48, "k_xtv_mfma_lds<%d,%d,%d,%d,fp4%s>", NRV, C, RB, W, MODE ? ",probe" : ""); \
-        return MIH_OK; }
+#define MIH_LDS(NRV, ID, C, RB, MODE, W) if (nr == NRV && mv6 == ID) \
+        MIH_LAUNCH((k_xtv_mfma_lds<NRV, C, RB, MODE, W>), W, C, "k_xtv_mfma_lds<%d,%d,%d,%d,fp4%s>", NRV, C, RB, W, MODE ? ",probe" : "")
     // FP4 digit planes through the LDS-DMA ring (tuning shapes)
     MIH_DMA(4, 20, 4, 4, 4, false, 0) MIH_DMA(4, 22, 2, 8, 4, false, 0) MIH_DMA(3, 20, 4, 4, 4, false, 0) MIH_DMA(2, 20, 4, 4, 4, false, 0)
     MIH_DMA(2, 22, 2, 8, 4, false, 0)
