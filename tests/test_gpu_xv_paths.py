@@ -313,16 +313,19 @@ def test_support_sizes_around_the_group_and_batch_boundaries(mih, tmp_path, env)
         _check_job(ref, jb, g, f"sizes[{env}] workspace {w}", exact_traits=lambda m: (0, m - 1))
 
 
-_MS = (2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 24, 25)
+_MS = (2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 16, 17, 24, 25, 31, 32)
 _MT_NNZ = (64, 1, 65, 7, 17, 8, 25, 9, 18, 16)          # not ascending: a short support finds a longer one's records behind its own
 
 
 @pytest.mark.parametrize("env", sorted(_ENVS))
 def test_trait_counts_cross_support_sizes(mih, tmp_path, env):
     """Every template of k_xv_snp_cached_mt (m <= 4, 6, 8, 10, 12), trait slots past m, two and three y-chunks (m = 13, 24, 25: the
-    second chunk's record reads run into the next record), against nnz with empty trailing groups (17: 9 of 16 groups), padding
-    of 7, 0 and 1 columns, per = 1 .. 5.  One workspace per m: the cache persists across the supports, the coefficient buffers
-    regrow (cap 72).  (a) runs on the first and the last trait, (b) and (c) on every trait."""
+    second chunk's record reads run into the next record), up to the largest trait count a multivariate fit accepts (m = 16, 17:
+    a second chunk of 4 and 5 traits; m = 31, 32: 12 + 12 + 7 and 12 + 12 + 8, records of 32 doubles of which the last is
+    padding at 31 and none is at 32), against nnz with empty trailing groups (17: 9 of 16 groups), padding of 7, 0 and 1 columns,
+    per = 1 .. 5.  One workspace per m: the cache persists across the supports, the coefficient buffers regrow (cap 72: the first
+    call's 64 m coefficients exceed it for every m >= 2, so the regrowth does not depend on the largest m).  (a) runs on the
+    first and the last trait, (b) and (c) on every trait."""
     n, p = 1003, 700
     rng = np.random.default_rng(20262)
     cols = make_bed(rng, n, p)
