@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset), and the kinship matrix and related-pair screen (mih_grm, mih_grm_pairs): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -209,6 +209,33 @@ int mih_snp_counts(const mih_mat *h, const uint8_t *row_keep, const uint8_t *col
  * that is not 2-bit, an empty selection, an index out of range, indices that are not strictly increasing. */
 int mih_snp_subset(const mih_mat *h, const int64_t *rows, int64_t nrows, const int64_t *cols, int64_t ncols,
                    int center, int scale, int impute, int dtype, mih_mat **out);
+/* The genetic relationship (kinship) matrix of the samples of a 2-bit or a 16-bit dosage handle (a dense handle: MIH_BAD_ARG),
+ * made entirely on the device -- SnpArrays.grm(x; method, minmaf) and the screen for pairs with Phi > 0.125 that
+ * manuscript/UKBB_metabolomic/data_process.jl:80-103 runs between SnpArrays.filter and the principal components
+ * (manuscript/NFBC_sim/NFBC_data_qc.jl:18-33 has GEMMA compute the same matrix).  Definitions (tests/grm_spec.py states them in
+ * numpy): C the kept columns, m = |C|; mu_j and sinv_j exactly what mih_snp_mu_sigma returns for the handle, whatever its
+ * center / scale / impute flags; c_ij = g_ij - mu_j for an observed genotype and 0 for a missing one (imputed by the mean;
+ * a column whose genotypes are all missing has mu = NaN and contributes exactly 0).
+ *   method 0, GRM:     Phi_ik = sum_{j in C} (c_ij sinv_j) (c_kj sinv_j) / (2 m): x_ij = c_ij sinv_j is the matrix a fit sees.
+ *   method 1, Robust:  Phi_ik = sum_{j in C} c_ij c_kj / (2 sum_{j in C, mu_j finite} mu_j (1 - mu_j / 2)).
+ * SnpArrays' third method, MoM, is not offered.  Float64 throughout on the f64 matrix pipe; every Phi_ik is summed over j in
+ * ascending order by a schedule that the shapes alone fix (no atomics on the accumulator, no split over the columns), so
+ * repeated calls agree bit for bit, whatever panel_cols; only the lower triangle is computed and the rest is its mirror
+ * image, so Phi == Phi' bit for bit.  col_keep: p bytes 0 / 1 in host memory, NULL = all.  panel_cols: how many kept columns
+ * are decoded to Float64 at a time, 0 = the library's rule (4096); a value that is not positive, or no multiple of 4, is
+ * rounded up.  Device memory: 8 n_pad^2 bytes (n_pad = n rounded up to 128) for the accumulator, 8 n_pad panel_cols for the
+ * panel, the lists; the sum is compared with the free memory before anything is allocated, and MIH_OOM names both byte
+ * counts.  Everything is released before the call returns; the handle is only read.
+ * mih_grm: phi receives the n x n matrix.
+ * mih_grm_pairs: the pairs (i, k), i < k (0-based), with Phi_ik > threshold (strictly; a NaN Phi_ik is no pair), in the order
+ * (i, k), so that no n x n array reaches the host.  *count = the pairs found; the first min(cap, *count) of them are written
+ * to row_i, row_k, phi and nothing beyond (with cap = 0 the three may be NULL); diag (n, may be NULL) receives Phi_ii.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: a dense handle, an empty column selection, an unknown
+ * method, cap < 0, a NaN threshold. */
+int mih_grm(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, double *phi /* n x n, host */);
+int mih_grm_pairs(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, double threshold,
+                  int64_t cap, int64_t *row_i, int64_t *row_k, double *phi, int64_t *count /* pairs found, may exceed cap */,
+                  double *diag /* n, may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

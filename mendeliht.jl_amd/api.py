@@ -174,6 +174,8 @@ def lib():
         "mih_snp_export_bed": [vp, vp],
         "mih_snp_counts": [vp, vp, vp, vp, vp],
         "mih_snp_subset": [vp, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
+        "mih_grm": [vp, vp, C.c_int, i64, vp],
+        "mih_grm_pairs": [vp, vp, C.c_int, i64, dbl, i64, vp, vp, vp, C.POINTER(i64), vp],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -230,7 +232,7 @@ def exported_symbols():
             "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -447,7 +449,70 @@ class _Mat:
 RESERVE_BY_DEFAULT = False
 
 
-class SnpLinAlg(_Mat):
+_GRM_METHODS = {"GRM": 0, "Robust": 1}
+
+
+class _Kinship:
+    """grm / related_pairs of the genotype handles (csrc/grm.hip: mih_grm, mih_grm_pairs)."""
+
+    def _grm_args(self, method, minmaf, cols):
+        if isinstance(method, str):
+            if method not in _GRM_METHODS:
+                raise ArgumentError(f"method must be 'GRM' or 'Robust', got {method!r}"
+                                    + (" (MoM is not offered)" if method == "MoM" else ""))
+            method = _GRM_METHODS[method]
+        if cols is None:
+            with np.errstate(invalid="ignore"):
+                ck = (self._allele_maf() >= minmaf).astype(np.uint8)              # (NaN fails)
+        else:
+            ck = SnpLinAlg._sel_mask(cols, self.p, "column")
+        return int(method), ck
+
+    def grm(self, method="GRM", minmaf=0.01, cols=None, panel_cols=0):
+        """SnpArrays.grm(x; method, minmaf): the (n, n) float64 kinship matrix of the samples, made on the device (mih_grm).
+        With mu_j and sinv_j of mu_sigma() and c_ij = g_ij - mu_j (0 for a missing genotype: imputed by the mean),
+        method "GRM" is Phi = X X' / (2 m) over the m kept columns with x_ij = c_ij sinv_j, the matrix a fit sees, and "Robust"
+        is Phi = C C' / (2 sum_j mu_j (1 - mu_j / 2)).  SnpArrays' third method, "MoM", is out of scope and refused.
+        cols: a boolean mask or a strictly increasing index array of the columns to use; None keeps the columns with
+        maf >= minmaf (a NaN maf fails), SnpArrays' default -- for a DosageMatrix the same rule on min(mu / 2, 1 - mu / 2).
+        panel_cols: kept columns decoded at a time, 0 = the library's rule.  Float64 on the f64 matrix pipe, every entry summed
+        over the columns in ascending order: Phi equals its transpose and a second call bit for bit.  The device needs
+        8 n^2 bytes for the call; MemoryError names the need and what is free."""
+        method, ck = self._grm_args(method, minmaf, cols)
+        try:
+            phi = np.empty((self.n, self.n))
+        except MemoryError:
+            phi = None                       # the library refuses first, with its byte counts, if the device cannot hold it either
+        rc = lib().mih_grm(self._h, _p(ck), method, int(panel_cols), _p(phi))
+        if phi is None and rc == 2:
+            raise MemoryError(f"the host cannot hold the {self.n} x {self.n} matrix: use related_pairs")
+        _check(rc)
+        return phi
+
+    def related_pairs(self, threshold=0.125, method="GRM", minmaf=0.01, cols=None, panel_cols=0, cap=None, _first_cap=None):
+        """The pairs of samples with Phi_ik > threshold (strictly) of grm(method, minmaf, cols), found on the device so that no
+        n x n array reaches the host (mih_grm_pairs): (i, k, phi, diag) with i < k in the order (i, k), phi bit-equal to the
+        entries of grm(), and diag the n values Phi_ii.  cap: the most pairs to return; None starts with room for
+        max(1024, 4 n) and calls once more with the count found if that was too small.
+        The screen of manuscript/UKBB_metabolomic/data_process.jl:84-101 is then
+            i, k, _, _ = x.related_pairs(0.125); mask = np.zeros(x.n, dtype=bool); mask[k] = True
+            x = x.subset(rows=~mask)"""
+        method, ck = self._grm_args(method, minmaf, cols)
+        room = int(cap) if cap is not None else int(_first_cap) if _first_cap is not None else max(1024, 4 * self.n)
+        diag = np.empty(self.n)
+        for _ in range(2):
+            i, k, phi = np.empty(max(room, 1), dtype=np.int64), np.empty(max(room, 1), dtype=np.int64), np.empty(max(room, 1))
+            count = C.c_int64(0)
+            _check(lib().mih_grm_pairs(self._h, _p(ck), method, int(panel_cols), float(threshold), room, _p(i), _p(k), _p(phi),
+                                       C.byref(count), _p(diag)))
+            if cap is not None or count.value <= room:
+                break
+            room = count.value
+        got = min(count.value, room)
+        return i[:got], k[:got], phi[:got], diag
+
+
+class SnpLinAlg(_Mat, _Kinship):
     """SnpLinAlg{Float64}(s::SnpArray; model=ADDITIVE_MODEL, center, scale, impute) on the GPU."""
 
     def _reserve(self, reserve):
@@ -551,6 +616,9 @@ class SnpLinAlg(_Mat):
         """SnpArrays.maf over the kept rows: min(f, 1 - f) with f the frequency of allele 2 among the non-missing genotypes
         (NaN for a column with none)."""
         return _maf_of(self.counts(rows=rows)[0])
+
+    def _allele_maf(self):
+        return self.maf()
 
     def missing_rate(self, axis):
         """The share of missing genotypes per column (axis = 0: over the rows, length p) or per row (axis = 1, length n)."""
@@ -723,7 +791,7 @@ class DenseMatrix(_Mat):
         return cls(None, device=device, _handle=h)
 
 
-class DosageMatrix(_Mat):
+class DosageMatrix(_Mat, _Kinship):
     """Genotype dosages d = num / denom in [0, 2] (VCF DS / GT, BGEN), resident in HBM as 16-bit numerators: 4x less memory
     and X'r traffic than the reference's Matrix{Float64} of the same values.  `num` is n x p, 0xFFFF marks a missing entry,
     1 <= denom <= 32767.  The matrix every fit sees is the STANDARDIZED one of standardize_genotypes! (src/wrapper.jl:406-423)
@@ -773,6 +841,10 @@ class DosageMatrix(_Mat):
         mu, s = np.empty(self.p), np.empty(self.p)
         _check(lib().mih_snp_mu_sigma(self._h, _p(mu), _p(s)))
         return mu, s
+
+    def _allele_maf(self):
+        f = self.mu_sigma()[0] / 2.0
+        return np.minimum(f, 1.0 - f)
 
     def regrid(self, denom):
         """The same matrix over the finer grid 1 / denom (a multiple of self.denom, at most 32767): every numerator times
