@@ -288,14 +288,23 @@ int mih_xtv_batched(const mih_mat *h, const double *R, int m, double *OUT);
  * point: their digits are zero, the scale is set by the largest of the REST, and k_xtv_finalize adds their terms g_ij r_i in f64
  * (m rows of the 2-bit matrix per column, only when the guard fires).  With one entry 1e8 or 1e12 x the rest every column, with or
  * without that row, is within 2 x 2^-53 sum_i g_ij |r_i| of the exact rational value (numpy's pairwise sum: 8 x) and within 1e-13 of
- * its own value unless that value has cancelled; a residual without such rows does not move a bit.  What is left: more than 64 rows
+ * its own value unless that value has cancelled; a residual without such rows does not move a bit.  For n < 16384 with a short or
+ * all-zero 256-row block (a single last row, the held-out rows of a contiguous fold) among the first few the guard's threshold is tiny or
+ * 0 and it may fire on ordinary residuals -- up to 64 ordinary rows then ride the side channel, or none; the result keeps the accuracy
+ * above either way (a cost, a rescan of the residual, not an error).  The side channel adds its terms in a compensated sum: one rounding
+ * of the result for up to 64 rows.  What is left: more than 64 rows
  * above the guard's threshold (a heavy TAIL rather than a few outliers) keep the plain scale, i.e. entry r_i keeps
  * 54 + log2(|r_i| / max|r|) bits -- 200 rows 1e6 x the rest: ~1e-7 on the columns that carry none of them.  A Poisson fit with a
  * planted count of 500 among counts of ~1 keeps the CPU restatement's loglikelihood trace to 1e-12 over 172 steps.
- * A residual with a NaN or +-Inf entry gives NaN in EVERY column of its row of OUT (the reference's floating-point mul! gives NaN or
- * +-Inf in every column that touches the entry -- all of them for a centered matrix); the other residuals of the call are untouched.
- * (tests/test_gpu_parity.py: test_xtv_fixed_point_under_adversarial_dynamic_range, test_peeled_rows_in_fused_passes_with_missing_genotypes,
- * test_poisson_fit_with_a_planted_count_outlier) */
+ * The scale is 2^-e with e = ebits - ilogb(max|r| of the rows in the fixed point), ebits = 53 (4910, 428), 56 (1316), 42 (4908), 26 (1308),
+ * capped at e = 1000 (a residual below 2^-947 is rounded to a quantum of 2^-1000); EVERY FINITE residual is scaled, up to max|r| = DBL_MAX
+ * (before, max|r| >= 1e300 kept e = 0 and gave a finite, wrong row).  A column whose exact value overflows comes out as +-Inf or NaN.
+ * A residual with a NaN or +-Inf entry, or whose sum overflows (two entries of 1.5e308), gives NaN in EVERY column of its row of OUT
+ * (the reference's floating-point mul! gives NaN or +-Inf in every column that touches the entry -- all of them for a centered matrix);
+ * the other residuals of the call are untouched.
+ * (tests/test_gpu_linalg.py: test_xtv_fixed_point_under_adversarial_dynamic_range, test_peeled_rows_in_fused_passes_with_missing_genotypes;
+ * tests/test_gpu_resident.py: test_poisson_fit_with_a_planted_count_outlier; tests/test_gpu_xtv_residual_edges.py: the guard, the scale
+ * rule and the side channel at their edges, against exact values) */
 int mih_xtv_batched_fmt(const mih_mat *h, const double *R, int m, int digits, double *OUT);
 /* out = sum_t x[:, idx[t]] * val[t]  -- the column loops of update_xb!
  * (src/utilities.jl:98-106) and iht_stepsize! (:731-739); idx 0-based. */

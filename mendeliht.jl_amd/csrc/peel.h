@@ -13,12 +13,23 @@
 //   * k_r_stats / k_res_stats leave max|r| per strided block of rows (block b: rows 256 b + t + 16384 k): B <= 64 non-empty blocks;
 //   * bq = the lower quartile of those block maxima (the ceil(B/4)-th smallest).  Up to ~3/4 of the blocks may hold outliers
 //     and bq is still a maximum of ordinary rows;
-//   * the guard fires iff max|r| > 64 bq.  Gaussian, Bernoulli, Poisson, log-normal residuals never get there (block maxima of
-//     7800 rows and the maximum of 500 000 differ by a factor 1.3 .. 10); then NOTHING changes, not a bit;
+//   * the guard fires iff max|r| > 64 bq (strictly: max|r| == 64 bq peels nothing).  With full blocks -- n >= 16384, every block a few
+//     hundred rows or more -- Gaussian, Bernoulli, Poisson, log-normal residuals never get there (block maxima of 7800 rows and the
+//     maximum of 500 000 differ by a factor 1.3 .. 10); then NOTHING changes, not a bit.  For n < 16384 the blocks are contiguous
+//     runs of 256 rows: the last one can hold a single row, and a block can be all zeros (the held-out rows of a contiguous fold).
+//     With four blocks or fewer the "quartile" is the SMALLEST block maximum (with five to eight the second smallest), so one small
+//     last row or one zero block makes tau tiny or 0 and the guard FIRES ON ORDINARY RESIDUALS: one workgroup rescans the n rows,
+//     and either more than kPeelMax rows lie above tau (nothing is peeled, the plain scale) or at most kPeelMax do -- ten rows of a
+//     Gaussian, every non-zero row of a sparse residual -- and they ride the side channel, exactly.  That is a cost (a rescan of
+//     n < 16384 rows per score), not an error: the result keeps its accuracy either way
+//     (tests/test_gpu_xtv_residual_edges.py: ragged, all-zero and single-row blocks, tau = 0, every non-zero row peeled, resident
+//     fits and cross-validation with whole blocks held out);
 //   * if it fires, ONE workgroup counts the rows with |r_i| > tau = 64 bq.  At most kPeelMax of them: they are peeled, listed by
 //     ascending row, and the scale comes from the largest |r_i| of the REST (<= tau).  More than kPeelMax (a heavy tail rather
 //     than a few outliers): no peel, the plain scale -- the documented 54 + log2(|r_i| / max|r|) bits.
-// A peeled residual keeps every entry of the rest to 2^-54 of the rest's maximum and every peeled entry exactly.
+// A peeled residual keeps every entry of the rest to 2^-54 of the rest's maximum and every peeled entry exactly; k_xtv_finalize adds the
+// peeled terms in a compensated sum (one rounding of the result for up to kPeelMax rows).  Every finite max|r| (up to DBL_MAX) has its
+// scale; only a NaN or +-Inf entry (or a sum r that overflows) leaves the fixed point -- NaN in every column, see k_xtv_finalize.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -30,6 +41,7 @@ constexpr int kPeelStride = 4 + 2 * kPeelMax;      // doubles per residual: [0] 
                                                    // [3] how often this slot's guard has fired (a running count, for the measurement hook),
                                                    // [4 ..) the rows (as doubles, ascending), [4 + kPeelMax ..) their r_i
 constexpr double kPeelRatio = 64.0;
+constexpr double kMaxFinite = 1.7976931348623157e308;   // x <= kMaxFinite: x is neither +Inf nor NaN (the scale rule of xtv_digits.hip uses it too)
 
 #if defined(__HIPCC__)
 // Whole workgroup (blockDim.x a multiple of 64, at most 1024 threads).  bpart[2 b] = max |r| of strided block b (the first
@@ -55,7 +67,7 @@ __device__ __forceinline__ double peel_decide(const double *__restrict__ r, int6
     }
     __syncthreads();
     const double fmx = nb > 0 ? s_fmx : 0.0, tau = kPeelRatio * (nb > 0 ? s_bq : 0.0);
-    if (!(fmx < 1.0e300) || !(fmx > tau)) {           // the common case: no outlier (or a non-finite residual: the scale's own rule)
+    if (!(fmx <= kMaxFinite) || !(fmx > tau)) {       // the common case: no outlier (or a non-finite residual: the scale's own rule)
         if (tid == 0) pl[0] = 0.0;
         return fmx;
     }

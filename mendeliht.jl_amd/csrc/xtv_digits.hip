@@ -57,9 +57,10 @@ k_r_stats(const double *__restrict__ r, int64_t n, int m, double *__restrict__ p
             fsm += __hip_atomic_load(&part[((int64_t)v * nblocks + b) * 2 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (top < 0.0) top = fmx;
-        // exponent e with top * 2^e < 2^(ebits+1) (DigitMode::ebits); an all-zero (or non-finite) residual keeps e = 0
+        // exponent e with top * 2^e < 2^(ebits+1) (DigitMode::ebits); an all-zero (or non-finite) residual keeps e = 0.  Every FINITE
+        // top has its exponent (e >= ebits - 1023: 2^e and 2^-e are finite); the same rule in k_digits' stats hook below
         int e = 0;
-        if (top > 0.0 && top < 1.0e300) e = ebits - ilogb(top);
+        if (top > 0.0 && top <= kMaxFinite) e = ebits - ilogb(top);
         if (e > 1000) e = 1000;          // a (numerically zero) residual below 2^-947: keep 2^e finite
         scal[4 * v + 0] = fmx;
         scal[4 * v + 1] = ldexp(1.0, -e);
@@ -105,7 +106,7 @@ k_digits(const double *__restrict__ r, int64_t n, int64_t nblk, int m, DigitMode
             for (int b = 0; b < 64; ++b) { fmx = fmax(fmx, sh.spart[2 * b]); fsm += sh.spart[2 * b + 1]; }
             const double top = (peel && peel[0] > 0.0) ? peel[2] : fmx;       // (k_res_peel took rows out: the scale of the rest)
             int e = 0;
-            if (top > 0.0 && top < 1.0e300) e = sh.ebits - ilogb(top);
+            if (top > 0.0 && top <= kMaxFinite) e = sh.ebits - ilogb(top);
             if (e > 1000) e = 1000;
             s_scale = ldexp(1.0, e);
             if (blockIdx.x == 0) { scal[0] = fmx; scal[1] = ldexp(1.0, -e); scal[2] = fsm; scal[3] = ldexp(1.0, e); }

@@ -772,12 +772,20 @@ __device__ __forceinline__ double xtv_finalize_col(int64_t j, const double *__re
     double dot = 0.0;
     for (int s = 0; s < splits; ++s) dot += pu[(int64_t)s * pstride + j];
     if (pl) {
+        // up to kPeelMax terms: a compensated sum (the rounding error of every addition is kept, exactly, and added at the end), so the
+        // side channel costs ONE rounding of the result however many rows it carries -- a plain chain of 64 additions was 2.5 x 2^-53
+        // sum_i g_ij |r_i| off when every non-zero row of a residual was peeled.  No row peeled: not an operation, not a bit.
         const int np = (int)pl[0];
+        double comp = 0.0;
         for (int t = 0; t < np; ++t) {
             const int64_t i = (int64_t)pl[4 + t];
             const uint32_t g = (X[xword(nbp, j, i >> 4)] >> (2 * (int)(i & 15))) & 3u;
-            dot += (double)g * pl[4 + kPeelMax + t];
+            const double x = (double)g * pl[4 + kPeelMax + t];          // exact
+            const double s = dot + x, bb = s - dot;
+            comp += (dot - (s - bb)) + (x - bb);
+            dot = s;
         }
+        if (np > 0 && fabs(comp) <= kMaxFinite) dot += comp;            // (a sum that overflowed stays +-Inf)
     }
     if (b > a) {
         double ms = 0.0;

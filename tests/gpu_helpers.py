@@ -157,7 +157,8 @@ def peel_rule(r, ratio=64.0, max_rows=64):
         rows = np.concatenate([np.arange(lo, min(lo + 256, n)) for lo in range(256 * b, n, 16384)])
         bmax[b] = a[rows].max()
     bq = np.sort(bmax)[(nb + 3) // 4 - 1]
-    tau = ratio * bq
+    with np.errstate(over="ignore"):
+        tau = ratio * bq
     if not (bmax.max() > tau) or not np.isfinite(bmax.max()):
         return np.zeros(0, dtype=np.int64)
     rows = np.flatnonzero(a > tau)
@@ -361,3 +362,207 @@ def dosage_xv_tol(num, den, idx, val, groups=16):
     c = np.where(ok, np.abs(sub.astype(np.float64) - mun[idx][None, :]), 0.0)
     w = np.abs(np.asarray(val, dtype=np.float64)) * sc[idx]
     return 2.0 * 2.0 ** -53 * ((per + G + 3) * (c @ w) + 2.0 * (ok.astype(np.float64) @ (w * mun[idx])))
+
+
+# ---- the residual front end of X'r over the 2-bit matrix at its edges: the scale rule restated, the inputs, exact values and bounds ----
+XTV_EBITS = {None: 53, 0: 53, 4910: 53, 4908: 42, 1316: 56, 1308: 26, 428: 53}      # DigitMode::ebits of csrc/xtv.hip's format table
+
+
+def peel_threshold(r, ratio=64.0):
+    """(tau, max|r|) of peel_rule's guard: tau = ratio x the ceil(B/4)-th smallest block maximum.  The guard fires iff max|r| > tau."""
+    a = np.abs(np.asarray(r, dtype=np.float64))
+    n = a.size
+    nb = min(64, (n + 255) // 256)
+    bmax = np.array([max(a[lo:lo + 256].max() for lo in range(256 * b, n, 16384)) for b in range(nb)])
+    with np.errstate(over="ignore"):
+        return float(ratio * np.sort(bmax)[(nb + 3) // 4 - 1]), float(bmax.max())
+
+
+def xtv_quantum(r, digits=None):
+    """The scale rule of the fixed-point residual restated (k_r_stats and the stats hook of k_digits, csrc/xtv_digits.hip): the quantum
+    2^-e every entry that stays in the fixed point is rounded to, e = ebits - ilogb(top) capped at 1000 (0 for top = 0), top = max|r|
+    over the rows peel_rule leaves in."""
+    import math
+    a = np.abs(np.asarray(r, dtype=np.float64)).copy()
+    a[peel_rule(r)] = 0.0
+    top = float(a.max())
+    if not (top > 0.0 and math.isfinite(top)):
+        return 1.0
+    return math.ldexp(1.0, -min(XTV_EBITS[digits] - (math.frexp(top)[1] - 1), 1000))
+
+
+def _codes(cols, n):
+    """PLINK codes (p x n) of packed columns; _pack is the way back."""
+    return np.stack([(cols >> s) & 3 for s in (0, 2, 4, 6)], axis=2).reshape(cols.shape[0], -1)[:, :n]
+
+
+def _pack(code):
+    p, n = code.shape
+    pad = np.zeros((p, (n + 3) // 4 * 4), np.uint8)
+    pad[:, :n] = code
+    return (pad[:, 0::4] | (pad[:, 1::4] << 2) | (pad[:, 2::4] << 4) | (pad[:, 3::4] << 6)).astype(np.uint8)
+
+
+class EdgeCase:
+    """One residual of the edge suite: r, the rows the guard is MEANT to peel (ascending), and what the result is held to:
+    "bound" (the derived bound), "bound_or_nan" (that, or NaN in every column) or "nan" (NaN in every column)."""
+    def __init__(self, name, r, rows=(), expect="bound", fires=None):
+        self.name, self.r, self.expect, self.fires = name, np.ascontiguousarray(r, dtype=np.float64), expect, fires
+        self.rows = np.array(sorted(int(i) for i in rows), dtype=np.int64)
+
+
+_EDGE_GROUPS = ("ragged", "zero_blocks", "limit", "where", "company", "scale", "huge")
+_EDGE_P = {"ragged": 37, "zero_blocks": 41, "limit": 48, "where": 70, "company": 37, "scale": 33, "huge": 35}
+
+
+def xtv_edge_problem(group, n):
+    """THE inputs of tests/test_gpu_xtv_residual_edges.py and of its CPU companion (which shows that every residual is what its name
+    says): (cols, cases) -- the packed PLINK columns of a p x n matrix (p = 33 .. 70: a ragged column group) and a list of EdgeCase.
+    Deterministic in (group, n).  Block b of the guard holds rows 256 b + t + 16384 k; nb = min(64, ceil(n / 256)) blocks, the guard's
+    quartile is the ceil(nb / 4)-th smallest block maximum.
+
+      ragged       a: Gaussian with the last row 2^-20; b: Gaussian; c: every entry +-1; d: Gaussian clipped to 2.5 with ten rows at +-3
+                   and the last row 2.75 / 64 -- where the last block is that single row and the quartile is the smallest maximum
+                   (n = 257, 513, 769) tau = 2.75 and exactly the ten rows are peeled, anywhere else nothing is
+      zero_blocks  z1 / z2: one / two whole blocks (and a single-row last block) zero, the rest Gaussian: tau = 0, more than 64 rows
+                   above it; nz64 / nz10 / nz1: only 64 / 10 / 1 non-zero rows: tau = 0 and every one of them is peeled
+      limit        lim64 / lim65: 64 / 65 rows 2^30 x the rest; tie: max|r| = 64 = 64 x the quartile exactly; tie_up: one ulp more
+      where        one row 1e9 x the rest: the last row, row 0, a row on which a column has a missing genotype (2 % missing)
+      company      23 residuals of the kinds above and plain Gaussians of several scales, one n
+      scale        max|r| = 2^k and the double below it, positive and negative, k = -1022, -600, 0, 1, 600; only denormal entries
+      huge         max|r| = 9.9e299, 1e300, 1e305, 2^1022 with every partial sum finite; two entries of 1.5e308 (sum r overflows)"""
+    assert group in _EDGE_GROUPS
+    rng = np.random.default_rng([20260 + _EDGE_GROUPS.index(group), n])
+    p = _EDGE_P[group]
+    nb = min(64, (n + 255) // 256)
+    clean = (nb + 3) // 4                                  # this many blocks must stay ordinary for the quartile to be ordinary
+    single_last = n < 16384 and n % 256 == 1 and n > 1
+    maf = rng.uniform(0.05, 0.5, p)
+    code = np.array([0, 2, 3], dtype=np.uint8)[rng.binomial(2, maf[:, None], size=(p, n))]
+    if group in ("where", "company"):
+        code[rng.random((p, n)) < 0.02] = 1
+    cases = []
+
+    def ragged(tag=""):
+        a = rng.standard_normal(n); a[n - 1] = 2.0 ** -20
+        b = rng.standard_normal(n)
+        c = rng.choice([-1.0, 1.0], n)
+        d = np.clip(rng.standard_normal(n), -2.5, 2.5)
+        ten = np.sort(rng.choice(n - 1, min(10, n - 1), replace=False))
+        d[ten] = 3.0 * rng.choice([-1.0, 1.0], ten.size)
+        d[n - 1] = 2.75 / 64
+        d_fires = single_last and nb <= 4
+        return [EdgeCase(tag + "a", a, fires=bool(single_last and nb <= 4)), EdgeCase(tag + "b", b), EdgeCase(tag + "c", c, fires=False),
+                EdgeCase(tag + "d", d, rows=ten if d_fires else (), fires=d_fires)]
+
+    def zero_blocks(tag=""):
+        assert single_last and nb >= 4
+        out = []
+        for name, blocks in (("z1", (1,)), ("z2", (0, 2))):
+            r = rng.standard_normal(n)
+            for b in blocks:
+                r[256 * b:256 * (b + 1)] = 0.0
+            r[n - 1] = 0.0                                  # the single-row last block: a whole block too
+            out.append(EdgeCase(tag + name, r, fires=True))
+        for cnt in (64, 10, 1):
+            r = np.zeros(n)
+            rows = np.sort(rng.choice(256 * (nb - clean), cnt, replace=False))      # the last `clean` blocks stay zero: tau = 0
+            r[rows] = 1.0 if cnt == 1 else rng.standard_normal(cnt) + np.where(rng.random(cnt) < 0.5, -0.1, 0.1)
+            assert np.count_nonzero(r) == cnt
+            out.append(EdgeCase(f"{tag}nz{cnt}", r, rows=rows, fires=True))
+        return out
+
+    def limit(tag=""):
+        base = rng.standard_normal(n)
+        cand = np.flatnonzero(np.abs(base) > 0.05)
+        cand = cand[cand >= 256 * clean]                    # the first `clean` blocks keep ordinary maxima
+        rows = np.sort(rng.choice(cand, 65, replace=False))
+        r64, r65 = base.copy(), base.copy()
+        r64[rows[:64]] *= 2.0 ** 30
+        r65[rows] *= 2.0 ** 30
+        tie = np.clip(rng.standard_normal(n) / 8, -0.99, 0.99)
+        tie[3:256 * nb:256] = rng.choice([-1.0, 1.0], len(tie[3:256 * nb:256]))       # every full block's maximum is exactly 1
+        if n % 256 and n - 256 * (nb - 1) <= 3:
+            tie[n - 1] = 1.0
+        at = int(256 * clean + 77)
+        up = tie.copy()
+        tie[at], up[at] = -64.0, -np.nextafter(64.0, np.inf)
+        return [EdgeCase(tag + "lim64", r64, rows=rows[:64], fires=True), EdgeCase(tag + "lim65", r65, fires=True),
+                EdgeCase(tag + "tie", tie, fires=False), EdgeCase(tag + "tie_up", up, rows=[at], fires=True)], rows
+
+    def where(tag=""):
+        miss_rows = np.flatnonzero((code == 1).any(axis=0))
+        mrow = int(miss_rows[miss_rows >= 300][0])
+        out = []
+        for name, row, val in (("last", n - 1, 1e9), ("first", 0, -3e8), ("missing", mrow, 2e9)):
+            r = rng.standard_normal(n); r[row] = val
+            out.append(EdgeCase(tag + name, r, rows=[row], fires=True))
+        return out
+
+    if group == "ragged":
+        cases = ragged()
+    elif group == "zero_blocks":
+        cases = zero_blocks()
+    elif group == "limit":
+        cases, rows = limit()
+        code[:8, rows] = 0                                  # columns 0 .. 7 carry none of the planted rows
+    elif group == "where":
+        cases = where()
+    elif group == "company":
+        lim, rows = limit("limit.")
+        special = ragged("ragged.") + zero_blocks("zero.") + lim + where("where.")[:2]
+        plain = [EdgeCase(f"gauss{t}", rng.standard_normal(n) * 10.0 ** s) for t, s in enumerate((0, -3, 5, 0, 100, -100, 1, 0))]
+        assert len(special) == 15 and len(plain) == 8
+        cases = [None] * 23
+        for t, c in enumerate(special + plain):
+            cases[(7 * t) % 23] = c                         # peeled and plain residuals interleaved over the two passes
+    elif group == "scale":
+        assert nb == 3 and single_last
+        for k in (-1022, -600, 0, 1, 600):
+            for vname, v in (("pow2", 2.0 ** k), ("below", float(np.nextafter(2.0 ** k, 0.0)))):
+                for sign in (1.0, -1.0):
+                    r = np.ldexp(np.clip(rng.standard_normal(n) / 4, -0.9, 0.9), k)
+                    if sign > 0:
+                        r[n - 1] = v                        # the single-row block holds the maximum: every block maximum >= max / 64
+                    else:
+                        r[100], r[n - 1] = -v, np.ldexp(0.5, k)
+                    cases.append(EdgeCase(f"{vname}_k{k}_{'pos' if sign > 0 else 'neg'}", r, fires=False))
+        r = rng.integers(-2 ** 20, 2 ** 20, n).astype(np.float64) * 2.0 ** -1074
+        r[n - 1] = 2.0 ** 21 * 2.0 ** -1074
+        cases.append(EdgeCase("denormal_only", r, fires=False))
+    else:
+        assert nb == 3 and single_last
+        for name, T in (("9.9e299", 9.9e299), ("1e300", 1e300), ("1e305", 1e305)):
+            r = T * np.clip(rng.standard_normal(n) / 4, -0.9, 0.9); r[n - 1] = T        # sum |r| < 513 x 0.9e305: no partial sum overflows
+            cases.append(EdgeCase("max_" + name, r, expect="bound_or_nan", fires=False))
+        r = 1e305 * np.clip(rng.standard_normal(n) / 4, -0.9, 0.9); r[100], r[n - 1] = -1e305, 0.5e305
+        cases.append(EdgeCase("max_1e305_neg", r, expect="bound_or_nan", fires=False))
+        T = 2.0 ** 1022                                                                   # the rest at 2^-10 T: sum |r| < 2 T < 2^1024
+        r = np.ldexp(np.clip(rng.standard_normal(n) / 4, -0.9, 0.9), 1012); r[n - 1], r[5], r[300] = T, T / 32, -T / 32
+        cases.append(EdgeCase("max_2p1022", r, expect="bound_or_nan", fires=False))       # (every block maximum >= T / 32: tau = 2 T)
+        r = np.ldexp(np.clip(rng.standard_normal(n) / 4, -0.9, 0.9), 1012); r[100], r[n - 1] = T, np.ldexp(0.5, 1012)
+        cases.append(EdgeCase("max_2p1022_outlier", r, rows=[100], expect="bound_or_nan", fires=True))
+        r = rng.standard_normal(n); r[7] = r[300] = 1.5e308; r[n - 1] = 1.0             # (tau = 64: the two rows and no other)
+        cases.append(EdgeCase("sum_overflows", r, rows=[7, 300], expect="nan", fires=True))
+        code[:, [100, n - 1]] = np.minimum(code[:, [100, n - 1]], 2)      # dosage <= 1 on the rows of 2^1022: the exact X'r stays below 2^1024
+    return _pack(code), cases
+
+
+def xtv_edge_exact(cols, n, case, digits=None):
+    """Exact X'r of the raw dosages (a missing entry counts as 0) against residual case.r, and the derived bounds, per column, as
+    Fractions: (exact, B, ulp_sum) with
+        B_j = (q / 2) sum_i g_ij [row i not peeled] + 8 x 2^-53 sum_i g_ij |r_i|,   q = xtv_quantum(r, digits),  ulp_sum_j = 2^-53 sum_i g_ij |r_i|
+    -- the rounding of every entry of the fixed point to its quantum, and the f64 recombination at the 8 ulp-sums numpy's own sum is
+    granted.  The sums are taken in integers (r_i = A_i / D with one power of two D)."""
+    from fractions import Fraction
+    g = _dosages(cols, n)
+    A, D = _dyadic(case.r)
+    N = _int_matvec(g, [int(v) for v in A])
+    S = _int_matvec(g, [abs(int(v)) for v in A])
+    inside = np.ones(n, dtype=np.int64)
+    inside[case.rows] = 0
+    cnt = g.astype(np.int64) @ inside
+    q = Fraction(xtv_quantum(case.r, digits))
+    exact = [Fraction(int(v), D) for v in N]
+    ulp = [Fraction(int(v), D) / 2 ** 53 for v in S]
+    return exact, [q / 2 * int(c) + 8 * u for c, u in zip(cnt, ulp)], ulp
