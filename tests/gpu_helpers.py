@@ -566,3 +566,278 @@ def xtv_edge_exact(cols, n, case, digits=None):
     exact = [Fraction(int(v), D) for v in N]
     ulp = [Fraction(int(v), D) / 2 ** 53 for v in S]
     return exact, [q / 2 * int(c) + 8 * u for c, u in zip(cnt, ulp)], ulp
+
+
+# ---- the matrix side of X'r over the 2-bit matrix: the row slices and the pass plan restated, inputs, exact values, counted bounds ----
+# DigitMode of csrc/xtv.hip's format table: (base, digits, residuals per operand, digit columns per residual)
+XTV_MODES = {None: (49, 10, 3, 10), 0: (49, 10, 3, 10), 4910: (49, 10, 3, 10), 4908: (49, 8, 4, 8), 1316: (13, 16, 2, 16),
+             1308: (13, 8, 4, 8), 428: (4, 28, 1, 32)}
+XTV_KERNELS = tuple(f"k_xtv_dma16<{nr},2,8,{3 if nr == 6 else 4}{h}>" for nr in range(1, 7) for h in ("", ",half")) + \
+    ("k_xtv_dma<1,2,4,8,fp4>", "k_xtv_mfma_lds<2,4,1,4,fp4>", "k_xtv_mfma_lds<3,2,2,8,fp4>", "k_xtv_mfma_lds<4,2,2,8,fp4>")
+
+
+def xtv_slices(n, p):
+    """auto_splits + row_slice of csrc/xtv.hip / xtv_kernels.h restated for n < 100000 rows: the number of 128-row blocks every row
+    slice walks, one entry per slice (0: an empty trailing slice -- its workgroups run one masked-out step).  nbp = ceil(n / 128)
+    blocks; the slice count s doubles while s < 16, ceil(ceil(p / 32) / 16) s < 2048 and nbp // (2 s) >= 8, and never exceeds nbp;
+    a slice holds bps = ceil(nbp / s) blocks, the last ones what is left."""
+    assert 1 <= n < 100000
+    nbp = -(-n // 128)
+    groups = (-(-p // 32) + 15) // 16
+    s = 1
+    while s < 16 and groups * s < 2048 and nbp // (2 * s) >= 8:
+        s *= 2
+    s = min(s, nbp)
+    bps = -(-nbp // s)
+    return [max(0, min(bps, nbp - k * bps)) for k in range(s)]
+
+
+def xtv_plan(digits, m, max_flat_passes=16):
+    """plan_passes + dispatch_xtv of csrc/xtv.hip restated at the release defaults (max_nr = 4, max_ops = 6, half = true): the passes
+    that score m residuals in format `digits`, as [(residuals, operands, half, kernel name)] -- the name is the string dispatch_xtv
+    leaves in the pass record.  The ten-digit format packs its digit columns flat (19 residuals in six operands) while that takes at
+    most 16 passes (m <= 304), and goes back to three residuals per operand beyond."""
+    base, ndig, per_op, slots = XTV_MODES[digits]
+    lay16 = base == 49
+
+    def name(nr, half):
+        if lay16:
+            return f"k_xtv_dma16<{nr},2,8,{3 if nr == 6 else 4}{',half' if half else ''}>"
+        return {1: "k_xtv_dma<1,2,4,8,fp4>", 2: "k_xtv_mfma_lds<2,4,1,4,fp4>", 3: "k_xtv_mfma_lds<3,2,2,8,fp4>",
+                4: "k_xtv_mfma_lds<4,2,2,8,fp4>"}[nr]
+    out = []
+    if lay16 and slots * per_op < 32:
+        cap = (6 * 32) // slots
+        npass = -(-m // cap)
+        if npass <= max_flat_passes:
+            for q in range(npass):
+                cnt = m // npass + (1 if q < m % npass else 0)
+                nr = (cnt * slots + 31) // 32
+                half = cnt * slots - 32 * (nr - 1) <= 16
+                out.append((cnt, nr, half, name(nr, half)))
+            return out
+    nops = -(-m // per_op)
+    t = 0
+    while t < nops:
+        rem = nops - t
+        if lay16:
+            np_ = -(-rem // 6)
+            nr = -(-rem // np_)
+        else:
+            nr = 4 if (rem >= 4 and rem != 5) else 3 if rem in (3, 5) else 2 if rem >= 2 else 1
+        u1 = min((t + nr) * per_op, m)
+        half = lay16 and (u1 - (t + nr - 1) * per_op) * slots <= 16
+        out.append((u1 - t * per_op, nr, half, name(nr, half)))
+        t += nr
+    return out
+
+
+def xtv_recombine_count(digits, splits):
+    """C of the matrix-side bound: how many ulp-sums u sum_i g_ij |r_i| (u = 2^-53) the f64 recombination of the exact digit sums can
+    cost, COUNTED from csrc/xtv_kernels.h (digit_weights, digit_sum / xtv_epilogue / xtv_epilogue16_flat, xtv_finalize_col).
+
+    The f32 accumulators are exact: S_t = sum_i g_ij d_it per digit plane t and slice, R_i = sum_t d_it b^t the integer residual.
+    Signed digits magnify: with |d| <= 2 (b - 1) / 3 in all three systems (32 / 48, 8 / 12, 2 / 3) the digits below the leading one
+    T_i add up to at most (2/3) b^T_i, so |R_i| >= b^T_i / 3 and sum_t |d_it| b^t <= (5/3) b^T_i <= K |R_i| with K = 5.
+      products  x_t = fl(S_t w_t): one rounding of a term of size <= sum_i g_ij |d_it| b^t  -> K ulp-sums over all t.  Base 4: w_t is a
+                power of two, no rounding (0).  Base 13 with 16 digits: w_15 = 4 x 13^15 > 2^53 is itself rounded (2 K); every other
+                weight (16 x 49^9, 4 x 13^7) is an integer below 2^53 times a power of two.
+      additions ten columns: the chain sum = ((0 + x_0) + x_1) + ... + x_9, nine roundings.  The partial sum after digit k is
+                sum_i g_ij (R_i mod-reduced to its digits <= k): |R_i| exactly for k >= T_i, at most (2/3) b^(k+1) <= 2 |R_i| b^(k+1-T_i)
+                below.  Worst T_i = 2: 8 + 2 + 2 / 49 -> 10 ulp-sums (rounded down by less than the slack below).
+                8 / 16 / 32 columns: the xor tree, log2(slots) levels; a level adds partial sums of arbitrary digit subsets, each
+                bounded by the magnified size -> K log2(slots).
+      scale     x 2^-e: exact.
+      slices    dot = ((0 + p_0) + p_1) + ... : splits - 1 roundings of at most the whole sum (an empty slice adds +0 exactly).
+      peeled    the compensated sum of the side channel: one rounding of the result and its own second-order term -> 2.
+      slack     1: second-order terms (C u << 1) and sum g |R| 2^-e against sum g |r| (a relative 2^-54 per row).
+    4910: 5 + 10 + splits + 2 = splits + 17;  4908: 5 + 15 + splits + 2;  1316: 10 + 20 + splits + 2;  1308: 5 + 15 + splits + 2;
+    428: 0 + 25 + splits + 2.  (The 8 of xtv_edge_exact was set on the measured side of this count; it does not survive it.)"""
+    base, ndig, per_op, slots = XTV_MODES[digits]
+    K = 5
+    products = 0 if base == 4 else 2 * K if (base, ndig) == (13, 16) else K
+    additions = 10 if slots == 10 else K * {8: 3, 16: 4, 32: 5}[slots]
+    return products + additions + (splits - 1) + 2 + 1
+
+
+def xtv_matrix_cols(n, p, miss=0.02, seed=0, last_row_missing=False):
+    """Packed PLINK columns (p x ceil(n / 4)) of the matrix-side tests: random genotypes with allele frequencies spread over
+    0.02 .. 0.5 and a share `miss` of missing codes; where p >= 9 the first eight columns are structured -- 0: all 0, 1: all 2,
+    2: a single 2 in row 0, 3: a single 1 in row n - 1, 4: non-zero only in the last (ragged) 128-row block, 5: non-zero only in rows
+    63, 64, 127, 128 (where they exist), 6: non-zero only in the last row of each row slice and the first of the next, 7: every
+    entry missing.  last_row_missing (p >= 10): column 8 has its only missing entry in row n - 1."""
+    rng = np.random.default_rng([20270, n, p, int(round(miss * 1000)), seed])
+    maf = rng.uniform(0.02, 0.5, p)
+    code = np.array([0, 2, 3], dtype=np.uint8)[rng.binomial(2, maf[:, None], size=(p, n))]
+    code[rng.random((p, n)) < miss] = 1
+    if p >= 9:
+        full = np.array([0, 2, 3], dtype=np.uint8)[rng.integers(1, 3, size=(8, n))]        # dosages 1 and 2 everywhere
+        code[:8] = 0
+        code[1] = 3
+        code[2, 0] = 3
+        code[3, n - 1] = 2
+        lo = 128 * ((n - 1) // 128)
+        code[4, lo:] = full[4, lo:]
+        rows = [i for i in (63, 64, 127, 128) if i < n]
+        code[5, rows] = full[5, rows]
+        bps = max(xtv_slices(n, p))
+        edge = [i for s in range(1, len(xtv_slices(n, p))) for i in (128 * bps * s - 1, 128 * bps * s) if i < n]
+        code[6, edge] = full[6, edge]
+        code[7] = 1
+    if last_row_missing:
+        assert p >= 10
+        code[8][code[8] == 1] = 0
+        code[8, n - 1] = 1
+    return _pack(code)
+
+
+def xtv_matrix_residuals(n, p, count=19):
+    """The residuals of the matrix-side tests for an n x p matrix, as EdgeCase (rows = what peel_rule peels: small n makes the guard
+    fire on ordinary residuals, and a unit vector rides the side channel as soon as n > 256 gives the guard a second block): unit vectors c e_i on rows 0, n - 1, 63, 64, 127,
+    128 and the slice boundaries 128 bps s - 1, 128 bps s (first, middle and last boundary), the constant 1, and Gaussian columns with
+    per-column scale exp(U(-3, 3)) -- dealt out so that every prefix of the list mixes the kinds: positions 0, 3, 5, 7, ... are
+    Gaussian, 1 is the constant, 2, 4, 6, ... the unit vectors while they last.  Deterministic in (n, p, count's prefix)."""
+    rng = np.random.default_rng([20271, n, p])
+    sl = xtv_slices(n, p)
+    bps = max(sl)
+    bnd = sorted({s for s in (1, len(sl) // 2, len(sl) - 1) if 1 <= s < len(sl)})
+    rows = [0, n - 1, 63, 64, 127, 128] + [i for s in bnd for i in (128 * bps * s - 1, 128 * bps * s)]
+    rows = [i for k, i in enumerate(rows) if 0 <= i < n and i not in rows[:k]]
+    out = []
+    while len(out) < count:
+        t = len(out)
+        if t == 1:
+            kind, r = "one", np.ones(n)
+        elif t >= 2 and t % 2 == 0 and rows:
+            i = rows.pop(0)
+            kind, r = f"unit{i}", np.zeros(n)
+            r[i] = float(np.exp(rng.uniform(-3, 3)) * rng.choice([-1.0, 1.0]))
+        else:
+            kind, r = f"gauss{t}", rng.standard_normal(n) * np.exp(rng.uniform(-3, 3))
+        out.append(EdgeCase(kind, r, rows=peel_rule(r)))
+    return out
+
+
+def xtv_matrix_exact(cols, n, case, splits):
+    """Exact X'r of the raw dosages against case.r (xtv_edge_exact, computed once) and, for every format, the bound
+        B_j = (q / 2) sum_i g_ij [row i not peeled] + C x 2^-53 sum_i g_ij |r_i|,  q = xtv_quantum(r, format), C = xtv_recombine_count(format, splits):
+    (exact, {format: bounds}, ulp_sum), Fractions per column."""
+    from fractions import Fraction
+    exact, b8, ulp = xtv_edge_exact(cols, n, case, 428)
+    q53 = Fraction(xtv_quantum(case.r, 428))
+    cnt = [(b - 8 * u) / (q53 / 2) for b, u in zip(b8, ulp)]                      # sum_i g_ij [row i not peeled], an integer
+    assert all(c.denominator == 1 for c in cnt)
+    bounds = {}
+    for dg in (None, 4908, 1316, 1308, 428):
+        q, C = Fraction(xtv_quantum(case.r, dg)), xtv_recombine_count(dg, splits)
+        bounds[dg] = [q / 2 * c + C * u for c, u in zip(cnt, ulp)]
+    return exact, bounds, ulp
+
+
+def xtv_std_exact(cols, n, case, mu, sinv, center, scale, impute, raw, w_stats=None):
+    """The exact value of the standardized X'r and its counted bound per column, from `raw` = xtv_matrix_exact(cols, n, case, splits):
+        exact_j = sinv_j (sum_i g_ij r_i + [impute] mu_j sum_{i missing in j} r_i - [center] mu_j sum_i r_i)
+    in rationals over the handle's own doubles mu_j, sinv_j (mu_sigma(); sinv_j = 1 without scale); a missing entry is stored as
+    dosage 0.  Returns (exact, {format: bounds}); exact_j is None where the reference itself has no value: a column with every entry
+    missing has mu = 0 / 0 = NaN, and with centring or imputation that NaN reaches the result (as in the reference's mean over no
+    observation) -- the result must then be NaN.
+
+    bound_j = |sinv_j| (B_j + u [ (k_j - 1) M_j + (w + 70) S_j + 6 (D_j + M_j + S_j) ]),  u = 2^-53, counted from xtv_finalize_col and k_r_stats:
+      D_j = sum_i g_ij |r_i|;  M_j = [impute] |mu_j| sum_{i missing in j} |r_i|;  S_j = [center] |mu_j| sum_i |r_i|;
+      (k_j - 1) M_j   the fix-up `ms += ru[miss_row[t]]` over the k_j missing rows: a plain chain, k_j - 1 roundings (0 + x is exact);
+      (w + 70) S_j    sum_r of k_r_stats: the thread's walk over w = ceil(n / 16384) rows (w - 1 roundings), 8 tree levels, the chain over
+                      64 block partials (63): w + 70;
+      6 (D + M + S)   dot += mu ms (product, sum), dot -= mu sum_r (product, difference), dot *= sinv: 5 roundings of at most the
+                      whole magnitude, and 1 for the second-order terms."""
+    from fractions import Fraction
+    exact_raw, bounds_raw, ulp = raw
+    p = cols.shape[0]
+    missing = (_codes(cols, n) == 1).astype(np.int64)
+    A, D = _dyadic(case.r)
+    Ai = [int(v) for v in A]
+    absA = [abs(v) for v in Ai]
+    msum = _int_matvec(missing, Ai); mabs = _int_matvec(missing, absA)
+    kmiss = missing.sum(axis=1)
+    sum_r, sum_abs = Fraction(sum(Ai), D), Fraction(sum(absA), D)
+    w = -(-n // 16384)
+    u = Fraction(1, 2 ** 53)
+    exact, bounds = [], {dg: [] for dg in bounds_raw}
+    for j in range(p):
+        nan = bool(np.isnan(mu[j])) and (center or (impute and kmiss[j] > 0))
+        m = Fraction(0) if np.isnan(mu[j]) else Fraction(float(mu[j]))
+        si = Fraction(float(sinv[j])) if scale else Fraction(1)
+        Mj = abs(m) * Fraction(int(mabs[j]), D) if impute else Fraction(0)
+        Sj = abs(m) * sum_abs if center else Fraction(0)
+        Dj = ulp[j] * 2 ** 53
+        val = exact_raw[j] + (m * Fraction(int(msum[j]), D) if impute else 0) - (m * sum_r if center else 0)
+        exact.append(None if nan else si * val)
+        tail = u * (max(int(kmiss[j]) - 1, 0) * Mj + (w + 70) * Sj + 6 * (Dj + Mj + Sj))
+        for dg in bounds:
+            bounds[dg].append(abs(si) * (bounds_raw[dg][j] + tail))
+    return exact, bounds
+
+
+def snp_host_stats(cols, n):
+    """mu_j and sinv_j as k_col_stats (csrc/snp.hip) forms them from the genotype counts: every operation a correctly rounded IEEE
+    one on both sides.  A column with every entry missing: mu = 0 / 0 = NaN, sinv = 1."""
+    code = _codes(cols, n)
+    n1, n2, nm = (code == 2).sum(axis=1).astype(np.float64), (code == 3).sum(axis=1).astype(np.float64), (code == 1).sum(axis=1).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = (n1 + 2.0 * n2) / (float(n) - nm)
+        s = np.sqrt(m * (1.0 - m / 2.0))
+        sinv = np.where(s > 0.0, 1.0 / s, 1.0)
+    return m, sinv
+
+
+# the cases of tests/test_gpu_xtv_matrix_edges.py (and of its CPU companion, which shows that the inputs are what their names say)
+XTV_ROW_N = (1, 3, 64, 127, 128, 129, 255, 384, 385, 512, 513, 640, 1024, 1025, 1152, 1920, 2048, 2049, 4095, 4225, 8321, 16400, 28800, 28801)
+XTV_RUNS = ((None, 1), (None, 19), (428, 1), (1316, 4), (1316, 6), (1316, 8), (4908, 5))        # (format, residuals in the call)
+XTV_COL_N = (385, 2049)
+XTV_COL_P = (1, 31, 32, 33, 64, 65, 255, 256, 257, 511, 512, 513, 545, 1025)
+XTV_PLAN_SHAPES = ((385, 70), (2049, 65))
+XTV_PLAN_M = {None: list(range(1, 20)) + [20, 38, 39, 304, 305, 307], 4908: [1, 3, 5, 8, 9, 12, 13, 16, 17, 20, 21, 24, 25],
+              1316: list(range(1, 15)) + [18], 428: list(range(1, 10)), 1308: [1, 4, 5, 16, 17]}
+XTV_FLAGS = ((1, 1, 1), (1, 1, 0), (0, 0, 1), (1, 0, 1))
+XTV_FLAG_SHAPES = ((129, 33), (2049, 65), (16400, 70))
+XTV_FLAG_MISS = (0.02, 0.3)
+XTV_FLAG_RUNS = ((None, 3), (428, 1))
+
+
+def xtv_run_calls(m, flags=False):
+    """The residuals (positions in xtv_matrix_residuals' list) of the calls a run of m residuals makes: the first m in one call; a run
+    of one makes three calls -- a Gaussian, the constant 1 and the unit vector on row n - 1 (position 4).  flags: the standardized
+    runs take the Gaussians and the constant (positions 0, 1, 3)."""
+    if flags:
+        return [[0, 1, 3]] if m == 3 else [[0], [1], [3]]
+    return [[0], [1], [4]] if m == 1 else [list(range(m))]
+
+
+class XtvMatrixProblem:
+    """One matrix of the matrix-side tests with its residuals; exact values and bounds are computed once per residual."""
+    def __init__(self, n, p, miss=0.02, count=19, last_row_missing=False):
+        self.n, self.p, self.miss = n, p, miss
+        self.cols = xtv_matrix_cols(n, p, miss, last_row_missing=last_row_missing)
+        self.cases = xtv_matrix_residuals(n, p, count)
+        self.slices = xtv_slices(n, p)
+        self.R = np.asfortranarray(np.stack([c.r for c in self.cases], axis=1))
+        self._raw, self._std = {}, {}
+
+    def raw(self, t):
+        if t not in self._raw:
+            self._raw[t] = xtv_matrix_exact(self.cols, self.n, self.cases[t], len(self.slices))
+        return self._raw[t]
+
+    def std(self, t, mu, sinv, flags):
+        if (t, flags) not in self._std:
+            self._std[(t, flags)] = xtv_std_exact(self.cols, self.n, self.cases[t], mu, sinv, *flags, self.raw(t))
+        return self._std[(t, flags)]
+
+
+_XTV_PROBLEMS = {}
+
+
+def xtv_matrix_problem(n, p, miss=0.02, count=19, last_row_missing=False):
+    key = (n, p, miss, count, last_row_missing)
+    if key not in _XTV_PROBLEMS:
+        _XTV_PROBLEMS[key] = XtvMatrixProblem(*key)
+    return _XTV_PROBLEMS[key]
