@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset), and the kinship matrix and related-pair screen (mih_grm, mih_grm_pairs): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset), and the kinship matrix and related-pair screen (mih_grm, mih_grm_pairs), and its leading eigenpairs (mih_grm_eig): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -236,6 +236,27 @@ int mih_grm(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel
 int mih_grm_pairs(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, double threshold,
                   int64_t cap, int64_t *row_i, int64_t *row_k, double *phi, int64_t *count /* pairs found, may exceed cap */,
                   double *diag /* n, may be NULL */);
+/* The k leading eigenpairs of that Phi -- the principal components of the standardised genotype matrix, as PLINK and GCTA
+ * compute them, which data_process.jl:103-110 hands to the fit as covariates -- without Phi leaving the device.  h, col_keep,
+ * method and panel_cols are mih_grm's.  values (k): the k largest eigenvalues, descending; vectors (n x k, column-major):
+ * vectors[i * n ..] is the unit eigenvector of values[i], its entry of largest magnitude (the lowest index on a tie) positive;
+ * residuals (k): |Phi u_i - lambda_i u_i|_2 as the device evaluated it for the returned pair; *converged = max_i residuals[i] <=
+ * tol * values[0]; *iters = products Phi Q taken.  Reaching max_iter is no error: the last Ritz pairs come back with
+ * *converged = 0 and their residuals.
+ * The method (tests/pca_spec.py states it in numpy): Phi, mirrored to the full symmetric n_pad x n_pad matrix, stays in device
+ * memory; a blocked subspace iteration with a block of b = block columns, 0 = round_up(max(2 k, k + 8), 16), at most n --
+ * a start hashed from (seed, row, column), Y = Phi Q on the f64 matrix pipe, Rayleigh-Ritz on Q'Y, and Q <- orth(orth(Y))
+ * through the eigen-decomposition of Y'Y, which drops a direction with d_i <= 2^-52 d_1 for the rest of the run.  The b x b
+ * algebra is the host's.  Every sum runs in an order the shapes fix, without atomics: the same arguments give the same bits,
+ * whatever panel_cols; another seed or block gives the same pairs within the tolerance, not bit for bit.
+ * Device memory: mih_grm's plus 8 (3 n_pad b + (n_pad / 512 + 4) b^2) bytes, checked in the same way before anything is
+ * allocated (MIH_OOM names both byte counts): 8 n_pad^2 bytes bound the route to about 170 000 samples on a 288 GB device.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: everything mih_grm refuses; k < 1 or k > min(n, 64); block
+ * not 0 and (< k or > 128); tol not finite or negative; max_iter < 1; a null result pointer.  MIH_BAD_ARG, too, with nothing
+ * written, when fewer than k directions survive: the message names the numerical rank found. */
+int mih_grm_eig(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, int32_t k, int32_t block, double tol,
+                int32_t max_iter, uint64_t seed, double *values /* k */, double *vectors /* n x k, column-major */,
+                double *residuals /* k */, int32_t *iters, int32_t *converged);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

@@ -7,6 +7,7 @@ Names, keyword arguments, defaults and error behaviour follow the reference:
   SnpLinAlg (SnpArrays.jl)             constructed as in src/wrapper.jl:68-69
 All numerics run in libmendeliht_hip.so on the GPU; this file only marshals.
 """
+import collections
 import ctypes as C
 import os
 import sys
@@ -176,6 +177,7 @@ def lib():
         "mih_snp_subset": [vp, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
         "mih_grm": [vp, vp, C.c_int, i64, vp],
         "mih_grm_pairs": [vp, vp, C.c_int, i64, dbl, i64, vp, vp, vp, C.POINTER(i64), vp],
+        "mih_grm_eig": [vp, vp, C.c_int, i64, i32, i32, dbl, i32, C.c_uint64, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -232,7 +234,7 @@ def exported_symbols():
             "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -451,9 +453,11 @@ RESERVE_BY_DEFAULT = False
 
 _GRM_METHODS = {"GRM": 0, "Robust": 1}
 
+PcaResult = collections.namedtuple("PcaResult", "values vectors residuals iters converged")
+
 
 class _Kinship:
-    """grm / related_pairs of the genotype handles (csrc/grm.hip: mih_grm, mih_grm_pairs)."""
+    """grm / related_pairs / pca of the genotype handles (csrc/grm.hip: mih_grm, mih_grm_pairs; csrc/pca.hip: mih_grm_eig)."""
 
     def _grm_args(self, method, minmaf, cols):
         if isinstance(method, str):
@@ -510,6 +514,28 @@ class _Kinship:
             room = count.value
         got = min(count.value, room)
         return i[:got], k[:got], phi[:got], diag
+
+    def pca(self, k, method="GRM", minmaf=0.01, cols=None, panel_cols=0, tol=1e-10, max_iter=500, block=0, seed=0):
+        """The k leading principal components of the samples: the k largest eigenvalues of grm(method, minmaf, cols) and their
+        eigenvectors, extracted on the device without the n x n matrix leaving it (mih_grm_eig) -- what PLINK and GCTA compute,
+        and the step after related_pairs in manuscript/UKBB_metabolomic/data_process.jl:103-110.  As covariates of a fit:
+            z = np.column_stack([np.ones(x.n), x.pca(10).vectors])
+        Returns PcaResult(values (k,) descending, vectors (n, k), residuals (k,), iters, converged): vectors[:, i] is the unit
+        eigenvector of values[i] with its entry of largest magnitude (the lowest index on a tie) positive; residuals[i] is
+        |Phi u_i - lambda_i u_i|_2 as the device evaluated it; converged says max(residuals) <= tol * values[0].  Reaching
+        max_iter is not an error: the last Ritz pairs come back with converged=False and their residuals.
+        method, minmaf, cols, panel_cols: those of grm().  1 <= k <= min(n, 64).  block: the columns of the blocked subspace
+        iteration, 0 = round_up(max(2 k, k + 8), 16), else k <= block <= 128; seed: of the hashed start block.  The same
+        arguments give the same bits, whatever panel_cols; another seed or block agrees within the tolerance.  A matrix of
+        numerical rank below k raises ArgumentError naming the rank.  The device needs 8 n^2 bytes for the call, like grm():
+        about 170 000 samples on a 288 GB device; MemoryError names the need and what is free."""
+        method, ck = self._grm_args(method, minmaf, cols)
+        k = int(k)
+        values, vectors, residuals = np.empty(max(k, 0)), np.empty((max(k, 0), self.n)), np.empty(max(k, 0))
+        iters, converged = C.c_int32(0), C.c_int32(0)
+        _check(lib().mih_grm_eig(self._h, _p(ck), method, int(panel_cols), k, int(block), float(tol), int(max_iter),
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, _p(values), _p(vectors), _p(residuals), C.byref(iters), C.byref(converged)))
+        return PcaResult(values, vectors.T, residuals, iters.value, bool(converged.value))
 
 
 class SnpLinAlg(_Mat, _Kinship):

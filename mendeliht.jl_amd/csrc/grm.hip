@@ -8,13 +8,12 @@
 // (K-major for a product over SNPs), and a symmetric rank-W update on the f64 matrix pipe adds the panel to an n_pad x n_pad
 // accumulator of which only the lower-triangular 128 x 128 tiles exist.  Every Phi_ik is one chain of fused multiply-adds over
 // the kept columns in ascending order, whatever the panel width: no atomics on the accumulator, no split over the columns.
-#include "common.h"
+#include "grm.h"
 #include <algorithm>
 #include <cmath>
 
 namespace mih {
 
-constexpr int kGrmTile = 128;              // the accumulator tile of one workgroup: four waves, 64 x 64 each
 constexpr int kGrmKB = 8;                  // panel columns per LDS stage (two steps of the 16 x 16 x 4 instruction)
 constexpr int kGrmLd = kGrmTile + 16;      // LDS row stride in doubles: the four panel columns a fragment load touches fall
                                            // into different halves of the 64 banks (144 mod 32 = 16)
@@ -221,15 +220,7 @@ k_grm_pairs(const double *__restrict__ Acc, int64_t n, int64_t n_pad, double div
     if (!off && live) cnt[kGrmPairParts * i + q] = c;
 }
 
-// What both entry points share: the checks, the memory rule, and the accumulator of the kept columns.
-struct GrmRun {
-    int64_t n = 0, n_pad = 0, m = 0;
-    double div = 0.0;
-    DevBuf<double> acc, panel;
-    DevBuf<int64_t> cols;
-};
-
-static int launch_failed(const char *what)
+int launch_failed(const char *what)
 {
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) return MIH_OK;
@@ -237,10 +228,8 @@ static int launch_failed(const char *what)
     return MIH_HIP_ERROR;
 }
 
-// extra_bytes: what the caller's finish will allocate on top (the pair lists); have_out: the caller's result pointers are there
-// (looked at after the memory rule, so that a caller who could not allocate an n x n result learns what the device lacks)
-static int grm_accumulate(const char *who, const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, double extra_bytes,
-                          bool have_out, GrmRun &g)
+int grm_accumulate(const char *who, const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, double extra_bytes,
+                   bool have_out, GrmRun &g)
 {
     if (!h) { set_error("%s: null matrix handle", who); return MIH_BAD_ARG; }
     if (h->kind != 0 && !h->Du) { set_error("%s needs a 2-bit (SnpLinAlg) or a 16-bit dosage handle, not a dense matrix", who); return MIH_BAD_ARG; }
@@ -312,6 +301,13 @@ static int grm_accumulate(const char *who, const mih_mat *h, const uint8_t *col_
     return MIH_OK;
 }
 
+int grm_mirror(GrmRun &g, hipStream_t s)
+{
+    const int64_t nt = g.n_pad / 32;
+    hipLaunchKernelGGL(k_grm_mirror, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, g.acc.p, g.n_pad, g.div);
+    return launch_failed("k_grm_mirror");
+}
+
 }  // namespace mih
 
 using namespace mih;
@@ -323,9 +319,7 @@ int mih_grm(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel
     GrmRun g;
     MIH_TRY(grm_accumulate("mih_grm", h, col_keep, method, panel_cols, 0.0, phi != nullptr, g));
     hipStream_t s = h->stream;
-    const int64_t nt = g.n_pad / 32;
-    hipLaunchKernelGGL(k_grm_mirror, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, g.acc.p, g.n_pad, g.div);
-    MIH_TRY(launch_failed("k_grm_mirror"));
+    MIH_TRY(grm_mirror(g, s));
     MIH_HIP(hipMemcpy2DAsync(phi, sizeof(double) * (size_t)g.n, g.acc.p, sizeof(double) * (size_t)g.n_pad, sizeof(double) * (size_t)g.n,
                              (size_t)g.n, hipMemcpyDeviceToHost, s));
     MIH_HIP(hipStreamSynchronize(s));
