@@ -3,6 +3,7 @@
 // translation unit that launches them gets its own copy.
 #pragma once
 #include "common.h"
+#include "scalar_log.h"
 #include <vector>
 #include <functional>
 #include <memory>

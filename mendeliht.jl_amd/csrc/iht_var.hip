@@ -636,13 +636,13 @@ int IhtVar::mu_loglik(int with_zc, double *logl, double *dev)
             double phi = o[0] / (double)n;           // utilities.jl:15: divides by length(y)
             double sd = std::sqrt(phi);
             // sum_i w_i * ( -(z_i^2 + log 2pi)/2 - log sd ),  z_i = (y_i-mu_i)/sd
-            *logl = -(o[0] / (sd * sd) + o[2] * 1.8378770664093454835606594728112) / 2.0 - o[2] * std::log(sd);
+            *logl = -(o[0] / (sd * sd) + o[2] * 1.8378770664093454835606594728112) / 2.0 - o[2] * scalar_log(sd);     // (scalar_log.h: the same bits as b_res_decide's on the device)
         } else if (dist == MIH_GAMMA) {          // sum_i w_i logpdf(Gamma(1/phi, mu_i phi), y_i)
             double phi = o[0] / (double)n, a = 1.0 / phi;
-            *logl = -o[2] * (std::lgamma(a) + a * std::log(phi)) - a * o[1] + (a - 1.0) * o[3];
+            *logl = -o[2] * (std::lgamma(a) + a * scalar_log(phi)) - a * o[1] + (a - 1.0) * o[3];
         } else if (dist == MIH_INVGAUSS) {       // sum_i w_i logpdf(InverseGaussian(mu_i, 1/phi), y_i)
             double lam = (double)n / o[0];
-            *logl = 0.5 * std::log(lam) * o[2] - 0.5 * o[3] - 0.5 * lam * o[0];
+            *logl = 0.5 * scalar_log(lam) * o[2] - 0.5 * o[3] - 0.5 * lam * o[0];
         } else *logl = o[1];
     }
     return MIH_OK;

@@ -1238,13 +1238,13 @@ b_res_decide(ResPtrs P, int epoch, int attempt, int next_attempt_queued, uint64_
     double logl;
     if (dist == MIH_NORMAL) {
         const double phi = o[0] / (double)n, sd = sqrt(phi);
-        logl = -(o[0] / (sd * sd) + o[2] * 1.8378770664093454835606594728112) / 2.0 - o[2] * log(sd);
+        logl = -(o[0] / (sd * sd) + o[2] * 1.8378770664093454835606594728112) / 2.0 - o[2] * scalar_log(sd);       // (scalar_log.h: the same bits as IhtVar::mu_loglik's on the host)
     } else if (dist == MIH_GAMMA) {
         const double phi = o[0] / (double)n, a = 1.0 / phi;
-        logl = -o[2] * (lgamma(a) + a * log(phi)) - a * o[1] + (a - 1.0) * o[3];
+        logl = -o[2] * (lgamma(a) + a * scalar_log(phi)) - a * o[1] + (a - 1.0) * o[3];
     } else if (dist == MIH_INVGAUSS) {
         const double lam = (double)n / o[0];
-        logl = 0.5 * log(lam) * o[2] - 0.5 * o[3] - 0.5 * lam * o[0];
+        logl = 0.5 * scalar_log(lam) * o[2] - 0.5 * o[3] - 0.5 * lam * o[0];
     } else logl = o[1];
     const int es = ctl->es, cur = ctl->cur;
     const double eta = res_halved(ctl->eta, es);

@@ -110,8 +110,9 @@ def _same_fit(a, b, what):
     assert a.iter == b.iter, (what, a.iter, b.iter)
     assert list(a.trace["backtracks"]) == list(b.trace["backtracks"]), what
     assert np.array_equal(np.flatnonzero(a.beta), np.flatnonzero(b.beta)), what
-    # every sum of the resident chain is formed in the host-driven kernels' order; only the scalar log / lgamma of the
-    # loglikelihood's closed form comes from another libm (device against host): the last bit of the trace may differ
+    # every sum of the resident chain is formed in the host-driven kernels' order, and the scalar log of the loglikelihood's closed
+    # form is csrc/scalar_log.h's on both sides; only the Gamma family's lgamma still comes from another libm (device against
+    # host): the last bit of a Gamma fit's trace may differ, every other trace is equal bit for bit
     np.testing.assert_allclose(a.trace["logl"], b.trace["logl"], rtol=4e-16, atol=0, err_msg=what)
     assert np.array_equal(a.trace["tol"], b.trace["tol"]), what
     assert np.array_equal(a.beta, b.beta) and np.array_equal(a.c, b.c), what
@@ -841,3 +842,366 @@ def xtv_matrix_problem(n, p, miss=0.02, count=19, last_row_missing=False):
     if key not in _XTV_PROBLEMS:
         _XTV_PROBLEMS[key] = XtvMatrixProblem(*key)
     return _XTV_PROBLEMS[key]
+
+
+# ---- project_k! at its buffer edges: the constants read from the sources, the list rules and the 22-bit prefix restated, the inputs ----
+_SELECT_PATTERNS = {
+    "topk.hip": {
+        "finish_cap": r"constexpr int kFinishCap = (\d+);",
+        "finish_bin": r"constexpr int kFinishBin = (\d+);",
+        "expect_pad": r"w\.expect = max_keep \+ (\d+);",
+        "cap_pad": r"w\.cap = max_keep \+ (\d+);",
+        "hist_blocks": r"gridh = \(int\)std::min<int64_t>\(\(len \+ 255\) / 256, (\d+)\)",
+        "sweep_blocks": r"gridh = [^;]*?, grid = \(int\)std::min<int64_t>\(\(len \+ 255\) / 256, (\d+)\);",
+        "radix_blocks": r"int grid = \(int\)std::min<int64_t>\(\(len \+ 255\) / 256, (\d+)\);\s*// <= 512 blocks",
+    },
+    "resident.inc": {
+        "collect_slots": r"constexpr int kResCollectSlots = (\d+);",
+        "collect_blocks": r"constexpr int kResCollectBlocks = (\d+);",
+        "grad_blocks": r"constexpr int kResGradBlocks = (\d+);",
+        "res_hist_blocks": r"constexpr int kResHistBlocks = (\d+);",
+        "max_in_bin": r"constexpr int kResMaxInBin = (\d+);",
+        "max_list": r"constexpr int kResMaxList = (\d+);",
+        "big_list": r"constexpr int kResBigList = (\d+);",
+        "spread_strides": r"const bool spread = len < (\d+) \* stride;",
+        "support_list": r"__shared__ int64_t lst_idx\[(\d+)\];",
+        "support_scan": r"if \(nl <= (\d+)\) \{ for \(int e = 0; e < nl; \+\+e\)",
+    },
+    "iht_var.hip": {         # a FIT sizes its stand-alone select with kcap, not with k: topk_work_init(topk, kcap)
+        "fit_kcap_floor": r"int64_t kcap = std::max<int64_t>\(std::max<int64_t>\(J, 1\) \* k \+ q, (\d+)\) \+ \d+;",
+        "fit_kcap_pad": r"int64_t kcap = std::max<int64_t>\(std::max<int64_t>\(J, 1\) \* k \+ q, \d+\) \+ (\d+);",
+        "fit_topk_by_kcap": r"MIH_TRY\(topk_work_init\(topk, kcap\)\);()",
+    },
+}
+_SELECT_CONSTANTS = {}
+
+
+def select_constants():
+    """The sizes the select's cases are built around, read from csrc/topk.hip and csrc/resident.inc (the cases follow the code); a
+    pattern that no longer matches exactly once is an AssertionError naming it."""
+    if not _SELECT_CONSTANTS:
+        import re
+        root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mendeliht.jl_amd", "csrc")
+        out = {}
+        for fname, pats in _SELECT_PATTERNS.items():
+            with open(os.path.join(root, fname)) as f:
+                text = f.read()
+            for name, pat in pats.items():
+                found = re.findall(pat, text)
+                assert len(found) == 1, f"{fname}: the pattern of {name} ({pat!r}) matches {len(found)} times, not once"
+                out[name] = int(found[0] or 1)
+        _SELECT_CONSTANTS.update(out)
+    return dict(_SELECT_CONSTANTS)
+
+
+def res_list_of(j, length, mode):
+    """Which of the per-block candidate lists of the resident select entry j of a vector of `length` = p + q entries lands in.
+    mode "direct": the gather of k_res_grad<true> -- block b owns the contiguous range [b chunk, (b + 1) chunk), chunk =
+    ceil(length / blocks); mode "collect": k_res_collect -- a vector shorter than 4 strides (stride = 256 blocks) is dealt out
+    entry by entry, j mod blocks; a longer one in runs of 256, (j // 256) mod blocks."""
+    C = select_constants()
+    assert C["collect_blocks"] == C["grad_blocks"]
+    B = C["collect_blocks"]
+    j = np.asarray(j, dtype=np.int64)
+    if mode == "direct":
+        return j // (-(-int(length) // B))
+    assert mode == "collect"
+    return j % B if length < C["spread_strides"] * B * 256 else (j // 256) % B
+
+
+def abs_key(x):
+    """The IEEE-754 bit pattern of |x| (monotone in |x|; -0.0 -> 0)."""
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64) & np.uint64(0x7FFFFFFFFFFFFFFF)
+
+
+def prefix22(x):
+    """Exponent and the top 11 mantissa bits of |x|: what two 11-bit histogram sweeps pin the threshold down to."""
+    return abs_key(x) >> np.uint64(41)
+
+
+def fit_select_caps(k, q, J=1):
+    """(expect, cap) of the stand-alone select INSIDE a fit (the host-driven step, the replay of a step the device handed back):
+    IhtVar sizes it with kcap = max(J k + q, 64) + 1024, so the landing buffer holds kcap + 64 pairs and the gather buffer
+    kcap + 1024 -- not k + 64 and k + 1024 as in mih.project_k."""
+    C = select_constants()
+    kcap = max(max(J, 1) * k + q, C["fit_kcap_floor"]) + C["fit_kcap_pad"]
+    return kcap + C["expect_pad"], kcap + C["cap_pad"]
+
+
+def tied_fit_route(copies, k=2, q=1):
+    """The way the stand-alone select takes inside the tied fits (k = 2, the intercept kept: K = 3) when every projection ties
+    copies + 1 entries at the threshold, above them only the intercept's +Inf: gathered = copies + 2 = survivors.  "host": within
+    the fit's gather buffer but more sharers than kFinishBin -- nth_element on the host, with the second copy when the landing
+    buffer is exceeded; "radix": beyond the gather buffer -- the 8 x 8-bit select, and compact_device grows its buffer."""
+    C = select_constants()
+    expect, cap = fit_select_caps(k, q)
+    tied, gathered = copies + 1, copies + 2
+    assert tied > C["finish_bin"]
+    return dict(route="radix" if gathered > cap else "host", fetch=gathered > expect, grow=gathered > cap, cap=cap, expect=expect)
+
+
+def select_counts(v, k, radix8=False):
+    """What the stand-alone select meets on vector v at sparsity k (csrc/topk.hip restated in counts): the entries above the
+    22-bit prefix of the k-th largest magnitude (A), the non-zero entries sharing it (S), the gathered count A + S (zeros are
+    not gathered), the survivors (|x| >= the k-th largest, ties kept, zeros excluded), and the way they take:
+      route  "device": gathered <= min(cap, kFinishCap) and S <= kFinishBin -- k_topk_finish; "host": gathered <= cap otherwise
+             -- nth_element on the host; "radix": gathered > cap = k + 1024 (or the switch MENDELIHT_TOPK_RADIX8) -- 8 x 8 bits
+      fetch  the landing buffer of k + 64 pairs (kFinishCap at most for the device finish) does not hold what comes home (the
+             survivors; the candidates for the host finish): a second copy fetches the rest
+      grow   radix only: more survivors than cap -- compact_device grows its buffer and runs again."""
+    C = select_constants()
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    keys = abs_key(v)
+    nz = v != 0.0
+    kth = np.partition(keys, keys.size - k)[keys.size - k]
+    pre = kth >> np.uint64(41)
+    top = keys >> np.uint64(41)
+    A = int(np.count_nonzero(top > pre))
+    S = int(np.count_nonzero((top == pre) & nz))
+    surv = int(np.count_nonzero((keys >= kth) & nz))
+    cap, expect = k + C["cap_pad"], k + C["expect_pad"]
+    gathered = A + S
+    if radix8 or gathered > cap:
+        route, fetch, grow = "radix", surv > min(expect, cap), surv > cap
+    elif gathered <= C["finish_cap"] and S <= C["finish_bin"]:
+        route, fetch, grow = "device", surv > min(expect, cap, C["finish_cap"]), False
+    else:
+        route, fetch, grow = "host", gathered > min(expect, cap), False
+    return dict(A=A, S=S, gathered=gathered, survivors=surv, rem=k - A, route=route, fetch=fetch, grow=grow, cap=cap, expect=expect)
+
+
+def sweep_handover(length):
+    """(last index the 4-way unrolled loop of k_hist11 reads, first index its tail reads) for a vector of `length`; None where a
+    part is empty.  blocks = min(ceil(length / 256), 512), stride = 256 blocks; thread g runs the unrolled body while
+    i + 3 stride < length from i = g in steps of 4 stride, then the tail in steps of stride."""
+    blocks = min(-(-length // 256), select_constants()["hist_blocks"])
+    stride = 256 * blocks
+    i = np.arange(length, dtype=np.int64)
+    g = i % stride
+    left = length - 1 - g - 3 * stride
+    n_unr = np.where(left >= 0, left // (4 * stride) + 1, 0)
+    unrolled = (i // stride) < 4 * n_unr
+    return (int(i[unrolled].max()) if unrolled.any() else None, int(i[~unrolled].min()) if (~unrolled).any() else None)
+
+
+class ProjectCase:
+    """One vector of the stand-alone select's edge cases: v, k and `want`, the entries of select_counts(v, k) its name promises."""
+    def __init__(self, name, v, k, **want):
+        self.name, self.v, self.k, self.want = name, np.ascontiguousarray(v, dtype=np.float64), int(k), want
+
+
+_PROJECT_CASES = []
+PROJECT_LENGTHS = (255, 256, 257, 512 * 256 - 1, 512 * 256, 512 * 256 + 1, 4 * 512 * 256 - 1, 4 * 512 * 256, 4 * 512 * 256 + 1)
+
+
+def project_cases():
+    """THE inputs of the stand-alone half of tests/test_gpu_select_edges.py (and of its CPU companion, which shows that every vector
+    sits where its name says).  Sharers of one 22-bit prefix are 1.0 + j 2^-52: distinct keys under the prefix of 1.0; entries
+    above them lie in [2, 1000), noise below in (0, 0.9); signs are mixed and the positions shuffled.  No NaN anywhere."""
+    if _PROJECT_CASES:
+        return list(_PROJECT_CASES)
+    C = select_constants()
+    FB, FC, EXP, CAP = C["finish_bin"], C["finish_cap"], C["expect_pad"], C["cap_pad"]
+    u = 2.0 ** -52
+    out = []
+
+    def build(tag, above, sharers, noise):
+        rng = np.random.default_rng([20280, *[ord(c) for c in tag]])
+        big = rng.uniform(2.0, 1000.0, above)
+        low = rng.uniform(1e-3, 0.9, noise)
+        v = np.concatenate([big, np.asarray(sharers, dtype=np.float64), low])
+        v *= rng.choice([-1.0, 1.0], v.size)
+        return rng.permutation(v)
+
+    # the sharers of the threshold's prefix against kFinishBin; k at the largest sharer, in their middle, at the smallest
+    for S in (FB - 1, FB, FB + 1):
+        for where, rank in (("largest", 1), ("middle", S // 2), ("smallest", S)):
+            v = build(f"sharers{S}{where}", 10, 1.0 + u * np.arange(S), 3000 - 10 - S)
+            out.append(ProjectCase(f"sharers S={S} k at the {where}", v, 10 + rank, A=10, S=S, gathered=10 + S, survivors=10 + rank,
+                                   rem=rank, route="device" if S <= FB else "host", fetch=S > FB and S > rank + EXP))
+    # the gathered candidates against kFinishCap, few sharers, cap = k + 1024 far away
+    for G in (FC - 1, FC, FC + 1):
+        k, S = FC - 46, G - (FC - 56)
+        v = build(f"candidates{G}", G - S, 1.0 + u * np.arange(S), 6000 - G)
+        out.append(ProjectCase(f"candidates A+S={G}", v, k, A=G - S, S=S, gathered=G, survivors=k, rem=10,
+                               route="device" if G <= FC else "host", fetch=G > k + EXP))
+    # t copies of the k-th magnitude: k - 1 + t survivors against the landing buffer of k + 64 pairs.  device: the ties are the
+    # only sharers; host: kFinishBin - 24 more sharers above them push the pool beyond kFinishBin, so the candidates come home
+    for t in (EXP, EXP + 1, EXP + 2):
+        v = build(f"ties_dev{t}", 49, np.full(t, 1.0), 3000 - 49 - t)
+        out.append(ProjectCase(f"threshold ties t={t}, device finish", v, 50, A=49, S=t, gathered=49 + t, survivors=49 + t, rem=1,
+                               route="device", fetch=t > EXP + 1))
+        more = FB - 24
+        v = build(f"ties_host{t}", 10, np.concatenate([1.0 + u * np.arange(1, more + 1), np.full(t, 1.0)]), 3000 - 10 - more - t)
+        k = 10 + more + 1
+        out.append(ProjectCase(f"threshold ties t={t}, host finish", v, k, A=10, S=more + t, gathered=k - 1 + t, survivors=k - 1 + t,
+                               rem=more + 1, route="host", fetch=t > EXP + 1))
+    # t copies against the gather buffer cap = k + 1024: beyond it the radix select runs and compact_device grows its buffer
+    for t in (CAP, CAP + 1, CAP + 2):
+        v = build(f"ties_cap{t}", 2, np.full(t, 1.0), 3000 - 2 - t)
+        over = 2 + t > 3 + CAP
+        out.append(ProjectCase(f"gather ties t={t}", v, 3, A=2, S=t, gathered=2 + t, survivors=2 + t, rem=1,
+                               route="radix" if over else "device" if t <= FB else "host", fetch=True, grow=over))
+    # degenerate inputs
+    rng = np.random.default_rng(20281)
+    for nnz in (99, 1, 0):
+        v = np.zeros(3000)
+        v[1::2] = -0.0
+        v[rng.choice(3000, nnz, replace=False)] = rng.standard_normal(nnz) + 3.0
+        out.append(ProjectCase(f"{nnz} non-zeros, k=100", v, 100, survivors=nnz, gathered=nnz, A=nnz, S=0, route="device"))
+    v = rng.standard_normal(3000)
+    out.append(ProjectCase("k = len", v, 3000, survivors=3000, gathered=3000, route="device"))
+    out.append(ProjectCase("len = 1", np.array([-0.75]), 1, survivors=1, gathered=1, A=0, S=1, route="device"))
+    out.append(ProjectCase("len = 1, zero", np.array([-0.0]), 1, survivors=0, gathered=0))
+    eq = 2.5 * rng.choice([-1.0, 1.0], 3000)
+    out.append(ProjectCase("all equal, k=7", eq, 7, A=0, S=3000, survivors=3000, route="radix", fetch=True, grow=True))
+    out.append(ProjectCase("all equal, k=len", eq, 3000, A=0, S=3000, survivors=3000, route="host", fetch=False))
+    for bits, route in ((52, "device"), (30, "radix")):      # exponent bin 0 throughout; below 2^-1044 all 3000 share ONE 22-bit prefix
+        den = rng.integers(1, 2 ** bits, 3000).astype(np.float64) * rng.choice([-1.0, 1.0], 3000) * 2.0 ** -1074
+        assert int(prefix22(den).max()) < 2048
+        out.append(ProjectCase(f"denormals only, below 2^{bits - 1074}", den, 50, route=route, grow=False, **(dict(S=3000) if bits == 30 else {})))
+    inf = rng.standard_normal(3000) * 1e300
+    inf[rng.choice(3000, 40, replace=False)] = np.repeat([np.inf, -np.inf], 20)
+    out.append(ProjectCase("40 infinities, k=25", inf, 25, A=0, S=40, survivors=40, route="device", fetch=False))
+    big = rng.standard_normal(3000) * 1e300
+    pos = rng.choice(3000, 20, replace=False)
+    big[pos[:10]] = np.repeat([np.inf, -np.inf], 5)
+    big[pos[10:]] = np.finfo(np.float64).max * np.repeat([1.0, -1.0], 5)
+    for k, surv in ((10, 10), (11, 20), (15, 20), (20, 20), (21, 21)):
+        out.append(ProjectCase(f"largest finite next to infinities, k={k}", big, k, survivors=surv, route="device"))
+    # lengths around the sweeps' geometry; the k-th and the (k + 1)-th largest (3 + 4 ulp and 3: one prefix, so the exact finish
+    # tells them apart) at the ends of the vector and on either side of the unrolled loop's hand-over to its tail
+    for L in PROJECT_LENGTHS:
+        last_unrolled, first_tail = sweep_handover(L)
+        spots = [(0, L - 1), (L - 1, 0)]
+        if last_unrolled is not None and first_tail is not None:
+            spots += [(last_unrolled, first_tail), (first_tail, last_unrolled)]
+        else:
+            spots += [(L // 2, L // 2 + 1), (L // 2 + 1, L // 2)]
+        base = np.random.default_rng([20282, L]).uniform(-0.9, 0.9, L)
+        for a, b in spots:
+            k = 37
+            v = base.copy()
+            free = np.setdiff1d(np.array([1, L // 3, L // 2 - 1, L - 2] + list(range(2, 200, 6))), [a, b])[:k - 1]
+            v[free] = np.linspace(4.0, 8.0, k - 1) * np.where(np.arange(k - 1) % 2, -1.0, 1.0)
+            v[a], v[b] = -(3.0 + 4 * 2.0 ** -51), 3.0
+            out.append(ProjectCase(f"len={L}, k-th at {a}, next at {b}", v, k, A=k - 1, S=2, gathered=k + 1, survivors=k, rem=1, route="device"))
+    _PROJECT_CASES.extend(out)
+    return list(out)
+
+
+# ---- the resident select inside fits: problems whose supports fill or overflow its lists ----
+_SELECT_BEDS = {}
+SELECT_FIT_N = 2000
+SELECT_LAYOUTS = {                       # name: (p, planted columns, k, max_iter)
+    "A": (41 * 512, tuple(5 + 512 * m for m in range(40)), 45, 8),
+    "B": (51200, tuple(range(10000, 10070)), 80, 8),
+    "B_exact64": (51200, tuple(range(10000, 10064)), 80, 8),
+    "B_exact65": (51200, tuple(range(10000, 10065)), 80, 8),
+}
+
+
+def planted_response(cols, n, planted, rng):
+    """y = X_S (+-1) + 0.5 + N(0, 1) over the standardized dosages of the planted columns (no missing entries)."""
+    g = _dosages(cols[np.asarray(planted)], n).astype(np.float64)
+    xs = (g - g.mean(axis=1, keepdims=True)) / g.std(axis=1, keepdims=True)
+    return rng.choice([-1.0, 1.0], len(planted)) @ xs + 0.5 + rng.standard_normal(n)
+
+
+def select_fit_problem(layout):
+    """(cols, y, planted, k, max_iter) of layouts A and B (SELECT_LAYOUTS): make_bed(default_rng(7), 2000, p, maf_lo=0.2), no
+    covariates beyond the intercept, so the projection selects among p + 1 entries.
+      A        40 effects at 5 + 512 m: j mod 512 = 5 for all -- ONE list of k_res_collect's spread rule takes 40 > 32 entries;
+               the contiguous ranges of the direct gather (42 entries) hold one each
+      B        70 effects at 10000 .. 10069: one contiguous range (9999 .. 10099) holds them all -- the direct gather's list
+               overflows and k_res_grad's support list (64) with it, so the binary-search branch runs; j mod 512 are distinct
+      B_exact  64 / 65 effects there: the last linear scan, the first binary search."""
+    from conftest import make_bed
+    p, planted, k, max_iter = SELECT_LAYOUTS[layout]
+    n = SELECT_FIT_N
+    if p not in _SELECT_BEDS:
+        _SELECT_BEDS[p] = make_bed(np.random.default_rng(7), n, p, maf_lo=0.2)
+    cols = _SELECT_BEDS[p]
+    y = planted_response(cols, n, planted, np.random.default_rng([7, len(planted)]))
+    return cols, y, np.asarray(planted), k, max_iter
+
+
+def select_tied_copies(copies):
+    """The positions tied_case copies SNP 300 to: `copies` consecutive positions from 400."""
+    return tuple(range(400, 400 + copies))
+
+
+def tied_copy_counts():
+    """The massive-tie fits: 2047 copies (2048 tied entries fill the resident pool exactly), 2100 (they overflow it), and as many
+    copies as the FIT's gather buffer holds pairs (fit_select_caps: 2112), so that the tied entries alone exceed it and the
+    host-driven replay runs the radix select inside a fit."""
+    return (2047, 2100, fit_select_caps(2, 1)[1])
+
+
+def clear_cut_backtracks(traces):
+    """How many leading entries the backtrack traces of the oracle on the input as given and under the nudges have in common: the
+    part of the trace that is not decided between loglikelihoods equal to rounding."""
+    traces = [list(map(int, t)) for t in traces]
+    n = 0
+    while all(len(t) > n for t in traces) and len({t[n] for t in traces}) == 1:
+        n += 1
+    return n
+
+
+TINY_N, TINY_SEED, TINY_MAX_ITER = 64, 7, 8
+TINY_COMBOS = tuple((p, q, k) for p in (1, 5, 511, 512, 513) for q in (1, 2) for k in sorted({1, p // 2, p} - {0}))
+
+
+def tiny_problem(p, q):
+    """(cols, y, z) of the tiny fits: 64 rows, min(3, p) planted effects, an intercept and (q = 2) one Gaussian covariate."""
+    from conftest import make_bed
+    rng = np.random.default_rng([TINY_SEED, p, q])
+    cols = make_bed(rng, TINY_N, p, maf_lo=0.2)
+    planted = np.sort(rng.choice(p, min(3, p), replace=False))
+    y = planted_response(cols, TINY_N, planted, rng)
+    z = np.column_stack([np.ones(TINY_N)] + [rng.standard_normal(TINY_N) for _ in range(q - 1)])
+    return cols, y, z
+
+
+def oracle_wavers(oracle, ox, y, z, tol=1e-5, **kw):
+    """True when the oracle's own fit moves by more than `tol` under the ulp-sized nudges of its covariates (_unstable)."""
+    pick = lambda d, g=1.0: dict(iter=d["iter"], beta=d["beta"], c=d["c"] * g, logl=d["logl"], bt=np.asarray(d["bt_trace"], dtype=float))
+    z = np.ones((len(y), 1)) if z is None else z
+    o = oracle.fit_iht(ox, y, z, **kw)
+    return any(_unstable(pick(o), pick(oracle.fit_iht(ox, y, z * g, **kw), g), tol) for g in _NUDGES)
+
+
+# combinations of TINY_COMBOS whose oracle trajectory moves under the nudges (tests/test_select_edges_cpu.py asserts the list): a
+# one-SNP model with the intercept alone is solved by the first exact line search, and every later backtracking decision compares
+# loglikelihoods that are equal to rounding
+TINY_DROPPED = ((1, 1, 1), (5, 1, 1), (511, 1, 1), (512, 1, 1))
+
+SELECT_C_N, SELECT_C_RUN, SELECT_C_WEIGHT = 400, 256 * 1000, 100.0      # layout C: rows, first column of the 40-column run, prior weight on it
+
+
+def select_layout_c(at_boundary, polymorphic=None):
+    """(p, planted) of layout C: 40 adjacent columns at the start of one 256-aligned run, p + 1 = 4 x 512 x 256 - 1 (k_res_collect
+    deals the vector out entry by entry: 40 lists) or 4 x 512 x 256 (runs of 256: ONE list).  polymorphic (a flag per column of the
+    matrix at hand: enough minor alleles to carry an effect): the first such run from column SELECT_C_RUN on whose 40 columns all
+    have the flag."""
+    C = select_constants()
+    length = C["spread_strides"] * C["collect_blocks"] * 256 - (0 if at_boundary else 1)
+    start = SELECT_C_RUN
+    if polymorphic is not None:
+        ok = np.asarray(polymorphic, dtype=bool)
+        start = next(s for s in range(SELECT_C_RUN, length - 1 - 256, 256) if ok[s:s + 40].all())
+    return length - 1, start + np.arange(40)
+
+
+def model_size_cases(q=3):
+    """(name, k, zkeep, where) of the model-size edges with q covariates: K = k + zkeepn, K + 64 against kResMaxList (the select in
+    LDS / in scratch memory) and kResBigList (resident at all).  where: "lds", "scratch" or "host"."""
+    C = select_constants()
+    out = []
+    for zkeep in (None, [1, 0, 1]):
+        zn = q if zkeep is None else sum(zkeep)
+        out.append((f"last LDS select, zkeepn={zn}", C["max_list"] - 64 - zn, zkeep, "lds"))
+        out.append((f"first scratch select, zkeepn={zn}", C["max_list"] - 64 - zn + 1, zkeep, "scratch"))
+    out.append(("last resident model", C["big_list"] - 64 - q, None, "scratch"))
+    out.append(("first model beyond the scratch lists", C["big_list"] - 64 - q + 1, None, "host"))
+    return out

@@ -901,7 +901,8 @@ def test_randomized_genotype_linear_algebra(mih, oracle):
 
 def test_randomized_projections(mih, oracle):
     """Seeded sweep of the two projections (utilities.jl:553-559, :613-679) on their own: lengths from 1 to a few hundred thousand
-    (around the 2 x 11-bit histogram passes of the device top-k and its 64 Ki-candidate host finish), k from 1 to the length,
+    (around the 2 x 11-bit histogram passes of the device top-k; no trial aims at a buffer limit of its finish -- those are the
+    cases of tests/test_gpu_select_edges.py), k from 1 to the length,
     heavy ties (values rounded to one or two digits, blocks of equal magnitudes with mixed signs), zeros, +-Inf, denormals;
     group labels dense or sparse with empty groups, J and k (scalar / vector) at random -- bit for bit against the oracle."""
     rng = np.random.default_rng(int(os.environ.get("MIH_SWEEP_SEED", 515)))
