@@ -52,7 +52,7 @@ typedef struct mih_mat mih_mat;     /* device-resident design matrix */
 int mih_device_count(int *count);
 /* thread-local message of the last failing call on this host thread */
 int mih_last_error(char *buf, size_t len);
-int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset), and the kinship matrix and related-pair screen (mih_grm, mih_grm_pairs), and its leading eigenpairs (mih_grm_eig): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
+int mih_version(int *major, int *minor);     /* 0.7: VCF text streamed into a dosage matrix (mih_vcf_*, mih_dosage_create_vcf), and hard calls packed into the 2-bit matrix on the device (mih_snp_builder_*, mih_snp_create_dosage, mih_snp_create_vcf), and counts and subsets of the 2-bit matrix (mih_snp_counts, mih_snp_subset), and the kinship matrix and related-pair screen (mih_grm, mih_grm_pairs), and its leading eigenpairs (mih_grm_eig), and the SNP correlation band and LD pruning (mih_ld_band, mih_ld_pairs, mih_ld_prune): additions, the version stays; 0.6: BGEN streamed into a dosage matrix (mih_dosage_create_bgen, mih_dosage_regrid); 0.5: the 16-bit dosage matrix (mih_dosage_*); 0.4: cv_threads, mih_cv_allgather, column-sharded lock-step drivers */
 /* sizeof(mih_fit_params), sizeof(mih_fit_result), sizeof(mih_mv_result), sizeof(mih_comm): lets a binding
  * check its struct mirrors against the library it loaded. */
 int mih_abi_sizes(int64_t *sizes, int32_t n);
@@ -257,6 +257,49 @@ int mih_grm_pairs(const mih_mat *h, const uint8_t *col_keep, int method, int64_t
 int mih_grm_eig(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, int32_t k, int32_t block, double tol,
                 int32_t max_iter, uint64_t seed, double *values /* k */, double *vectors /* n x k, column-major */,
                 double *residuals /* k */, int32_t *iters, int32_t *converged);
+/* The correlation of SNP pairs inside a window of columns (linkage disequilibrium) of a 2-bit handle and the pruning of its
+ * columns by it, made on the device -- what `plink --indep-pairwise` does between SnpArrays.filter and the kinship matrix in
+ * manuscript/NFBC_sim/NFBC_data_qc.jl:18-33; the mask goes to mih_grm / mih_grm_pairs / mih_grm_eig as col_keep.  Definitions
+ * (tests/ld_spec.py states them in numpy): g_ij in {0, 1, 2} an observed genotype, miss(j) the missing rows of column j,
+ * m_j = |miss(j)|, n_j = n - m_j, s_j = sum of the observed g_ij, mu_j = s_j / n_j whatever the handle's center / scale / impute
+ * flags; t_ij = g_ij where observed and 0 where missing.  The LD of two columns is the correlation of the mean-imputed columns
+ * (c_ij = g_ij - mu_j where observed, 0 where missing: the c_ij of mih_grm):
+ *   D_jk = sum_i t_ij t_ik,  A_jk = sum_{i in miss(j)} t_ik,  M_jk = |miss(j) & miss(k)|            (integers, exact)
+ *   C_jk = D_jk - mu_j (s_k - A_jk) - mu_k (s_j - A_kj) + mu_j mu_k (n - m_j - m_k + M_jk),   C_jj = D_jj - s_j^2 / n_j
+ *   r_jk = C_jk / sqrt(C_jj C_kk)
+ * in Float64, the operations in this order, each rounded by itself.  A column is degenerate when n_j = 0 or n_j D_jj = s_j^2
+ * (monomorphic among its observed genotypes), decided in integers; it has r = 0 with every column.  Without a missing genotype
+ * in either column this is the r that --indep-pairwise thresholds; with missing genotypes PLINK takes the samples observed in
+ * both columns, and this library imputes by the mean, as everywhere else.
+ * The band holds the pairs j < k with k - j < w, w = min(window, p).  The integers come from the matrix cores: the tiles of
+ * two column groups are the A and the B operand of the FP4 instruction as they are stored.  They are exact, so the results
+ * are bit for bit the same whatever panel_cols and slice_rows, and on repeated calls.  panel_cols: the columns whose band is
+ * on the device at a time, 0 = the library's rule (4096, fewer for a wide window), else rounded up to a multiple of 32.
+ * slice_rows: the rows one f32 accumulator covers, rounded up to a multiple of 128 and never more than 2^22 -- up to there the
+ * sums are exact, so a larger value is taken as 2^22; 0 = the library's rule: 2^22, fewer where a launch would have too few
+ * work items to fill the device.
+ * Device memory beyond the handle: a panel's mask image (1024 bytes per tile of its column groups and of those the window
+ * reaches; none for a matrix without missing genotypes), its integer partial sums, its band, the pair list and 40 p bytes; the
+ * sum is compared with the free memory before anything is allocated, and MIH_OOM names both byte counts.  Everything is
+ * released before the call returns; the handle is only read.
+ * mih_ld_band: r (p x (w - 1) doubles, host): r[j (w - 1) + d - 1] = r_{j, j + d}, NaN where j + d >= p.  stats (may be NULL):
+ * the same shape x 4 int64, D_jk, A_jk, A_kj, M_jk of k = j + d (zeros where j + d >= p).  diag (p, may be NULL): D_jj.
+ * mih_ld_pairs: the pairs j < k of the band with r_jk r_jk > threshold (strictly, on the Float64 product; 0-based), in the order
+ * (j, k), so that no p x w array reaches the host.  *count = the pairs found; the first min(cap, *count) of them are written to
+ * col_j, col_k, r and nothing beyond (with cap = 0 the three may be NULL).
+ * mih_ld_prune: keep (p bytes) receives the 0 / 1 mask of the greedy pass over that list, run on the host (tests/ld_spec.py,
+ * prune): degenerate columns are dropped first; for s = 0, step, 2 step, ... < p the window is the columns [s, min(s + w, p));
+ * inside it i ascends over the kept columns and k over the kept columns above i; where r_ik^2 > threshold and maf(i) < maf(k),
+ * i is dropped and its loop left, otherwise k is dropped (a tie keeps the earlier column).  maf = min(f, 1 - f) of the exact
+ * counts, f = (n1 + 2 n2) / (2 (n0 + n1 + n2)).  *n_pairs (may be NULL) = the pairs above the threshold.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: a handle that is not 2-bit, window < 2, step < 1, a NaN
+ * threshold, cap < 0, a null result pointer. */
+int mih_ld_band(const mih_mat *h, int64_t window, int64_t panel_cols, int64_t slice_rows, double *r /* p x (w - 1), host */,
+                int64_t *stats /* p x (w - 1) x 4, may be NULL */, int64_t *diag /* p, may be NULL */);
+int mih_ld_pairs(const mih_mat *h, int64_t window, double threshold, int64_t panel_cols, int64_t slice_rows, int64_t cap,
+                 int64_t *col_j, int64_t *col_k, double *r, int64_t *count /* pairs found, may exceed cap */);
+int mih_ld_prune(const mih_mat *h, int64_t window, int64_t step, double threshold, int64_t panel_cols, int64_t slice_rows,
+                 uint8_t *keep /* p bytes */, int64_t *n_pairs /* may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

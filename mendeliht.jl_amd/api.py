@@ -178,6 +178,9 @@ def lib():
         "mih_grm": [vp, vp, C.c_int, i64, vp],
         "mih_grm_pairs": [vp, vp, C.c_int, i64, dbl, i64, vp, vp, vp, C.POINTER(i64), vp],
         "mih_grm_eig": [vp, vp, C.c_int, i64, i32, i32, dbl, i32, C.c_uint64, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)],
+        "mih_ld_band": [vp, i64, i64, i64, vp, vp, vp],
+        "mih_ld_pairs": [vp, i64, dbl, i64, i64, i64, vp, vp, vp, C.POINTER(i64)],
+        "mih_ld_prune": [vp, i64, i64, dbl, i64, i64, vp, C.POINTER(i64)],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -234,7 +237,7 @@ def exported_symbols():
             "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -656,6 +659,53 @@ class SnpLinAlg(_Mat, _Kinship):
         _check(lib().mih_snp_counts(self._h, None, None, None, _p(row_missing)))      # from the missing lists alone
         return row_missing / float(self.p)
 
+    # ---- linkage disequilibrium and pruning on the device (csrc/ld.hip) ----
+    def _ld_window(self, window):
+        return max(min(int(window), self.p), 1)
+
+    def ld(self, window, stats=False, panel_cols=0, slice_rows=0):
+        """The correlation r of every pair of columns j < k with k - j < window (clamped to p), made on the device (mih_ld_band):
+        a (p, w - 1) float64 array with r[j, d - 1] = r_{j, j + d} and NaN where j + d >= p.  r is the correlation of the
+        mean-imputed columns (the c_ij of grm()): without missing genotypes in either column what `plink --indep-pairwise`
+        thresholds; with missing genotypes PLINK takes the pairwise-complete samples, and this library imputes by the mean.
+        A column without an observed genotype, or monomorphic among its observed ones, has r = 0 with every column.
+        stats=True: (r, stats, diag) with stats (p, w - 1, 4) int64 -- D_jk, A_jk, A_kj, M_jk of tests/ld_spec.py -- and diag
+        (p,) int64, D_jj.  panel_cols: the columns whose band is on the device at a time; slice_rows: the rows one f32
+        accumulator covers; 0 = the library's rules.  The bits do not depend on either, nor on the call."""
+        w = self._ld_window(window)
+        r = np.empty((self.p, w - 1))
+        st = np.empty((self.p, w - 1, 4), dtype=np.int64) if stats else None
+        dg = np.empty(self.p, dtype=np.int64) if stats else None
+        _check(lib().mih_ld_band(self._h, int(window), int(panel_cols), int(slice_rows), _p(r), _p(st), _p(dg)))
+        return (r, st, dg) if stats else r
+
+    def ld_pairs(self, window, threshold, cap=None, panel_cols=0, slice_rows=0):
+        """The pairs of columns j < k, k - j < window, with r_jk^2 > threshold (strictly) of ld(window), found on the device so
+        that no p x window array reaches the host (mih_ld_pairs): (j, k, r) in the order (j, k), r bit-equal to the entries of
+        ld().  cap: the most pairs to return; None starts with room for max(1024, 4 p) and calls once more with the count
+        found if that was too small."""
+        room = int(cap) if cap is not None else _ld_first_room(self.p)
+        for _ in range(2):
+            j, k, r = np.empty(max(room, 1), dtype=np.int64), np.empty(max(room, 1), dtype=np.int64), np.empty(max(room, 1))
+            count = C.c_int64(0)
+            _check(lib().mih_ld_pairs(self._h, int(window), float(threshold), int(panel_cols), int(slice_rows), room, _p(j), _p(k), _p(r),
+                                      C.byref(count)))
+            if cap is not None or count.value <= room:
+                break
+            room = count.value
+        got = min(count.value, room)
+        return j[:got], k[:got], r[:got]
+
+    def ld_prune(self, window=50, step=5, r2=0.2, panel_cols=0, slice_rows=0):
+        """`plink --indep-pairwise window step r2` on the device's pair list (mih_ld_prune): a boolean mask over the columns.
+        Degenerate columns are dropped first; then the window [s, s + window) moves by step, and of every pair of kept columns
+        inside it with r^2 > r2 the one with the smaller maf goes (a tie keeps the earlier column).  The r is ld()'s.  The step
+        of manuscript/NFBC_sim/NFBC_data_qc.jl:18-33 between filter and the kinship matrix is then
+            keep = x.ld_prune(50, 5, 0.2); pcs = x.pca(10, cols=keep)"""
+        keep = np.empty(self.p, dtype=np.uint8)
+        _check(lib().mih_ld_prune(self._h, int(window), int(step), float(r2), int(panel_cols), int(slice_rows), _p(keep), None))
+        return keep.astype(np.bool_)
+
     def subset(self, rows=None, cols=None, center=None, scale=None, impute=None, dtype=None, reserve=None):
         """x[rows, cols] as a new SnpLinAlg, made on the device (mih_snp_subset): bit for bit the SnpLinAlg of the .bed encoding
         of the selected genotypes, with mu and 1/sigma over the kept rows.  rows, cols: boolean masks or strictly increasing
@@ -696,6 +746,11 @@ class SnpLinAlg(_Mat, _Kinship):
                 return rmask, cmask
         warnings.warn(f"filter: maxiters = {maxiters} reached, the success rates may not be satisfied", stacklevel=2)
         return rmask, cmask
+
+
+def _ld_first_room(p):
+    """The pairs ld_pairs(cap=None) makes room for before it knows their number."""
+    return max(1024, 4 * p)
 
 
 def _maf_of(col_counts):
