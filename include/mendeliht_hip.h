@@ -314,6 +314,21 @@ int mih_mat_destroy(mih_mat *h);
  * matrix -- bytes = 0: sized from its dimensions by the library's rule, bytes > 0: that size -- or releases it (bytes < 0).
  * Not to be called while a fit is running on the matrix.  MIH_OOM if the device has less than four times the size free. */
 int mih_mat_reserve(mih_mat *h, int64_t bytes);
+/* The score image of a 2-bit matrix: a second, derived image of the (immutable) matrix that only the single-residual X'r pass
+ * of a fit reads (residual format 428).  Columns with at most max_hom_fraction * n dosage-2 entries are stored at ONE bit per
+ * genotype (the plane g >= 1) with the rows of their dosage-2 entries in side lists, the other columns as they are; the pass
+ * over it gives bit for bit the results of the pass over the matrix and moves fewer bytes.  mode: MIH_IMAGE_BUILD builds it
+ * (replacing an earlier one; max_hom_fraction <= 0: the library's default; MIH_BAD_ARG if no column qualifies), MIH_IMAGE_RELEASE
+ * drops it, MIH_IMAGE_QUERY changes nothing; every mode then reports the image's bytes and its one-bit columns (0, 0: no image;
+ * either pointer may be NULL).  The image is a cache: fits and sessions started while it exists use it and keep it alive while
+ * they live; mih_device_trim, and any allocation of the library that runs out of device memory, release the images nobody uses.
+ * An argument, not an environment switch. */
+#define MIH_IMAGE_QUERY 0
+#define MIH_IMAGE_BUILD 1
+#define MIH_IMAGE_RELEASE 2
+int mih_mat_score_image(mih_mat *h, int mode, double max_hom_fraction, int64_t *bytes, int64_t *class1_cols);
+/* Releases every score image on the device that no live fit or session is using; released_bytes (may be NULL): how much. */
+int mih_device_trim(int device, int64_t *released_bytes);
 int mih_mat_dims(const mih_mat *h, int64_t *n, int64_t *p);
 /* `x.μ`, `x.σinv` of the SnpLinAlg, or mu_j (dosage units) and 1/sigma_j (1 where sigma_j = 0) of a dosage handle */
 int mih_snp_mu_sigma(const mih_mat *h, double *mu, double *sinv);

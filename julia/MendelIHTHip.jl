@@ -96,6 +96,19 @@ end
 
 # the reserve of device memory a matrix keeps for its fits (automatic from 4 GiB; bytes = 0: the library's sizing, < 0: release)
 reserve!(x::HipSnpLinAlg; bytes::Integer=0) = (check(ccall((:mih_mat_reserve, LIB), Cint, (Ptr{Cvoid}, Int64), x.handle, bytes)); x)
+# the score image of a matrix (the single-residual pass of a fit reads it; same bits, fewer bytes): mode 0 = query (the default, as in the Python mirror), 1 = build
+# (max_hom_fraction <= 0: the library's default), 2 = release; returns (bytes, one-bit columns) of the image the matrix has then
+function score_image!(x::HipSnpLinAlg; mode::Integer=0, max_hom_fraction::Real=0.0)
+    nbytes = Ref{Int64}(0); cols = Ref{Int64}(0)
+    check(ccall((:mih_mat_score_image, LIB), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ptr{Int64}, Ptr{Int64}), x.handle, mode, max_hom_fraction, nbytes, cols))
+    (nbytes[], cols[])
+end
+# releases every score image on the device that no live fit or session is using; the bytes released
+function device_trim(device::Integer=0)
+    nbytes = Ref{Int64}(0)
+    check(ccall((:mih_device_trim, LIB), Cint, (Cint, Ptr{Int64}), device, nbytes))
+    nbytes[]
+end
 
 # naive_impute(x, destination) (utilities.jl:862-899) on the device copy of the genotypes
 function naive_impute(x::HipSnpLinAlg{Float64}, destination::String)

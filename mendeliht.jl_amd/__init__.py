@@ -11,7 +11,7 @@ is missing.
 """
 from .api import (  # noqa: F401
     Bernoulli, IdentityLink, IHTResult, LogitLink, LogLink, MendelIHTError, MvNormal, NegativeBinomial,
-    Normal, Poisson, SnpLinAlg, SnpBuilder, DenseMatrix, DosageMatrix, cross_validate, cv_iht, device_count, fit_iht, iht,
+    Normal, Poisson, SnpLinAlg, SnpBuilder, DenseMatrix, DosageMatrix, cross_validate, cv_iht, device_count, device_trim, fit_iht, iht,
     library_path, mIHTResult, project_group_sparse, project_k, read_bed, standardize, lib, IHTSession,
     profile_enable, profile_read, profile_passes, cv_assignment, profile_counters, profile_exchange, EXCHANGE_KINDS, busy_union_ms, hash_folds, probe_set, using_probes,
     probes_library_path, iht_run_many_models, set_xtv_digits, set_step_mode, Gamma, InverseGaussian, ProbitLink,
@@ -24,6 +24,6 @@ __all__ = [
     "fit_iht", "cv_iht", "iht", "cross_validate", "project_k", "project_group_sparse", "SnpLinAlg",
     "DenseMatrix", "DosageMatrix", "SnpBuilder", "parse_genotypes", "read_vcf_snp", "read_bgen_snp", "IHTResult", "mIHTResult", "Normal", "Bernoulli", "Poisson", "NegativeBinomial",
     "MvNormal", "Gamma", "InverseGaussian", "IdentityLink", "LogitLink", "LogLink", "ProbitLink", "CloglogLink",
-    "CauchitLink", "InverseLink", "InverseSquareLink", "SqrtLink", "canonicallink", "maf_weights", "simulate_random_snparray", "simulate_random_response", "read_bed", "standardize", "device_count",
+    "CauchitLink", "InverseLink", "InverseSquareLink", "SqrtLink", "canonicallink", "maf_weights", "simulate_random_snparray", "simulate_random_response", "read_bed", "standardize", "device_count", "device_trim",
     "library_path", "MendelIHTError", "lib", "dist", "iht_run_many_models", "IHTSession", "naive_impute", "PcaResult",
 ]

@@ -171,6 +171,8 @@ def lib():
         "mih_mat_destroy": [vp],
         "mih_mat_dims": [vp, C.POINTER(i64), C.POINTER(i64)],
         "mih_mat_reserve": [vp, i64],
+        "mih_mat_score_image": [vp, C.c_int, dbl, C.POINTER(i64), C.POINTER(i64)],
+        "mih_device_trim": [C.c_int, C.POINTER(i64)],
         "mih_snp_mu_sigma": [vp, vp, vp],
         "mih_snp_export_bed": [vp, vp],
         "mih_snp_counts": [vp, vp, vp, vp, vp],
@@ -237,6 +239,7 @@ def exported_symbols():
             "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
+            "mih_mat_score_image", "mih_device_trim",
             "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
@@ -267,6 +270,13 @@ def device_count():
     n = C.c_int(0)
     _check(lib().mih_device_count(C.byref(n)))
     return n.value
+
+
+def device_trim(device=0):
+    """Releases every score image on the device that no live fit or session uses (mih_device_trim); the bytes released."""
+    nbytes = C.c_int64(0)
+    _check(lib().mih_device_trim(int(device), C.byref(nbytes)))
+    return nbytes.value
 
 
 # ---- distributions and links (Distributions.jl / GLM.jl names) -----------------------
@@ -590,6 +600,16 @@ class SnpLinAlg(_Mat, _Kinship):
         x = cls(None, center=center, scale=scale, impute=impute, device=device, _handle=h)
         x._reserve(reserve)
         return x
+
+    def score_image(self, mode="query", max_hom_fraction=0.0):
+        """The score image of the matrix (mih_mat_score_image): a derived image only the single-residual X'r pass of a fit reads
+        (residual format 428), with the columns that hold at most max_hom_fraction * n dosage-2 entries at one bit per genotype.
+        mode "build" (max_hom_fraction <= 0: the library's default), "release" or "query"; returns (bytes, one-bit columns) of the
+        image the matrix has afterwards, (0, 0) if none.  Results are bit for bit those of the 2-bit pass."""
+        code = {"query": 0, "build": 1, "release": 2}[mode]
+        nbytes, c1 = C.c_int64(0), C.c_int64(0)
+        _check(lib().mih_mat_score_image(self._h, code, float(max_hom_fraction), C.byref(nbytes), C.byref(c1)))
+        return nbytes.value, c1.value
 
     def mu_sigma(self):
         mu, s = np.empty(self.p), np.empty(self.p)

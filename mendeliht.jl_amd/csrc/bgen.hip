@@ -370,7 +370,7 @@ int mih_dosage_create_bgen(const char *path, int64_t n, int64_t ncols, const int
     } stg;
     for (;;) {                         // a failed allocation degrades to one worker before it fails the create
         const bool ok = hipHostMalloc((void **)&stg.pin, buf_bytes * 2 * nth, hipHostMallocDefault) == hipSuccess &&
-                        hipMalloc((void **)&stg.raw, buf_bytes * 2 * nth) == hipSuccess &&
+                        device_malloc((void **)&stg.raw, buf_bytes * 2 * nth) == hipSuccess &&
                         hipHostMalloc((void **)&stg.flag_pin, sizeof(uint32_t) * 4 * nth, hipHostMallocDefault) == hipSuccess;
         if (ok) break;
         (void)hipGetLastError();

@@ -53,6 +53,20 @@ constexpr int kChunkRows = 1024;
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// Every device allocation of the library.  The score images of 2-bit matrices (score_image.hip) are caches: when the device is
+// out of memory the unpinned ones of the current device are released (trim_score_images) and the allocation is tried once more.
+size_t trim_score_images(int device);
+inline hipError_t device_malloc_bytes(void **q, size_t bytes)
+{
+    hipError_t e = hipMalloc(q, bytes);
+    if (e != hipErrorOutOfMemory) return e;
+    (void)hipGetLastError();
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || trim_score_images(dev) == 0) return e;
+    return hipMalloc(q, bytes);
+}
+template <typename T> inline hipError_t device_malloc(T **q, size_t bytes) { return device_malloc_bytes((void **)q, bytes); }
+
 // A large matrix keeps a reserve of device memory for the fits that will run on it (DevPool): the lock-step lanes' workspaces
 // and the IHTVariables' blocks are cut out of it, so a fit never calls hipMalloc / hipFree.  Reasons: (1) on this driver the
 // first hipMalloc that lands in a large never-used block of VRAM stalls ~2.9 s while the block is cleared -- in 7 of 16 fresh
@@ -69,7 +83,7 @@ struct DevPool {
     bool init(size_t total)
     {
         total = (total + kGran - 1) / kGran * kGran;
-        if (hipMalloc((void **)&base, total) != hipSuccess) { (void)hipGetLastError(); base = nullptr; return false; }
+        if (device_malloc_bytes((void **)&base, total) != hipSuccess) { (void)hipGetLastError(); base = nullptr; return false; }
         bytes = total; free_blocks[0] = total;
         return true;
     }
@@ -115,7 +129,7 @@ inline hipError_t dev_malloc(void **q, size_t bytes, DevPool **from)
     if (DevPool *pl = current_pool()) {
         if (bytes >= (1ull << 20)) { if (void *r = pl->take(bytes)) { *q = r; *from = pl; return hipSuccess; } }
     }
-    return hipMalloc(q, bytes);
+    return device_malloc_bytes(q, bytes);
 }
 
 // An IHTVariable owns ~26 device and ~5 pinned buffers.  One hipMalloc of a few MB costs ~100 us and every hipFree ~150 us
@@ -300,6 +314,7 @@ MIH_LOCAL bool prof_begin(const ::mih_mat *h, hipStream_t s, PassRecord &rec);
 MIH_LOCAL void prof_end(const ::mih_mat *h, hipStream_t s, PassRecord &rec);
 }  // namespace mih
 
+namespace mih { struct ScoreImage; }
 // Device-resident design matrix.
 //
 // kind 0 (SnpLinAlg): 2-bit dosage codes in a TILE-MAJOR layout built for the matrix cores.
@@ -343,6 +358,11 @@ struct mih_mat {
     // the life of the matrix -- hipStreamCreate costs ~4 ms, a fresh set per cross-validation would cost more than it saves.
     mutable std::mutex ws_mu;
     mutable std::vector<hipStream_t> worker_streams;
+    // The score image (score_image.hip): a derived image of this immutable matrix that only the single-residual X'r pass reads.  A
+    // cache: whoever runs passes on it holds a reference (XtvWork::img, the pin), mih_device_trim drops the handle's own.
+    mutable std::mutex img_mu;
+    mutable std::shared_ptr<const mih::ScoreImage> img;
+    mutable bool img_declined = false;     // the automatic rule has looked at this matrix and built nothing: it does not look again
 };
 namespace mih {
 int select_device(int device);                 // hipSetDevice after checking that the device exists (MIH_NO_DEVICE / MIH_BAD_ARG)
@@ -411,6 +431,11 @@ struct DigitMode {
     // device-resident steps (iht_var.hip): the digit kernel and the single-fit pass run only while *gate == gate_val -- a chain queued
     // ahead of the host's knowledge (a step that turned out to need backtracking, a fit that converged) then does nothing
     const int32_t *gate = nullptr; int32_t gate_val = 0;
+    // a single-residual pass over the score image: k_digits also leaves U = R + 0x00AA..AA of every row (hom_u); the image kernels
+    // write partial[image position -> img_col] with the row stride img_pstride, and the one-bit kernel adds the digit sums
+    // img_hom[slice][class-1 position][32] of the dosage-2 entries it multiplied as 1
+    unsigned long long *hom_u = nullptr;
+    const int32_t *img_col = nullptr; const float *img_hom = nullptr; int64_t img_pstride = 0, img_p1 = 0;
 };
 // flat packing: which pass a residual rides and where the pass's operands start (k_digits)
 constexpr int kMaxFlatPasses = 16;
@@ -473,6 +498,10 @@ struct XtvWork {            // scratch for one in-flight X'r
     DigitMode dm_alt = {49, 8, 4, 8, 42, 18}; bool has_alt = false, use_alt = false;
     XtvSupportHook hook;       // ... and whose finalize kernel also serves the support of the iterate
     XtvStatsHook shook;        // ... and whose digit kernel finishes those statistics
+    // the matrix's score image, pinned for the life of the workspace (single-residual 428 workspaces only), and its scratch
+    std::shared_ptr<const ScoreImage> img;
+    DevBuf<unsigned long long> hom_u;   // n_pad : U of every row (k_digits)
+    DevBuf<float> hom;                  // splits * class-1 positions * 32 : digit sums of the dosage-2 entries (k_xtv_hom)
 };
 // batched = false: the workspace of a single univariate fit (one residual per pass); true: fused multi-RHS passes
 int  xtv_work_init(const mih_mat *h, XtvWork &w, int m, const XtvTune &tune, bool batched = true);
@@ -486,6 +515,29 @@ MIH_LOCAL void launch_r_stats(const double *r_dev, int64_t n, int m, double *par
                     const int32_t *gate, int32_t gate_val, double *peel, hipStream_t s);
 MIH_LOCAL void launch_digits(const double *r_dev, int64_t n, int64_t nblk, int m, int slots, const DigitMode &dm, double *scal, uint4 *dig, uint2 *dig2,
                    const FlatPasses &fp, const XtvStatsHook &sh, const double *peel, hipStream_t s);
+// score_image.hip: the image, its row slicing and the kernels of a pass over it
+struct ScoreImage {
+    int device = 0, splits = 0, nss = 0;       // row slices of the pass (auto_splits of the handle), sub-slices per slice
+    double tau = 0.0;
+    int64_t nbp = 0, ncg2 = 0, nt1 = 0, p1 = 0;  // class-2 column groups, class-1 tiles (two groups each), class-1 columns
+    int64_t pos1 = 0;                          // class-1 positions = 2 * nt1 * 32
+    char *tiles = nullptr;                     // ncg2 * nbp KB in the matrix's tile format, then nt1 * nbp KB of one-bit tiles
+    int32_t *col_of = nullptr;                 // image position -> column of the matrix (-1: pad); class 2 first
+    uint32_t *seg_off = nullptr;               // [(slice * pos1 + class-1 position) * nss + sub-slice], + 1 : a list's start, in 8 entries
+    uint16_t *rows = nullptr;                  // the lists: row numbers inside the sub-slice, ascending, padded to 8 entries
+    int32_t *order = nullptr;                  // [pos1] : class-1 positions by falling number of dosage-2 entries (k_xtv_hom's threads)
+    size_t bytes = 0;
+    ~ScoreImage();
+};
+constexpr int kHomSubBlocks = 64;              // a sub-slice: 64 blocks of 128 rows (8 k rows = 64 KB of U in LDS: two workgroups of k_xtv_hom a CU)
+std::shared_ptr<const ScoreImage> score_image_of(const mih_mat *h);
+MIH_LOCAL int xtv_default_splits(const mih_mat *h, const DigitMode &dm);       // xtv.hip: the row slices of a library-default pass
+// set-up of a fit or session that will run single-residual passes: builds the image if the automatic rule says so (never fails the fit)
+void score_image_auto(const mih_mat *h);
+// xtv.hip: a single-residual workspace with this tuning runs the pass the image serves (the 428 format, the product's kernel and row slices)
+bool xtv_rides_image(const mih_mat *h, const XtvTune &tune);
+void score_image_forget(const mih_mat *h);     // the handle is going away
+MIH_LOCAL void launch_xtv_hom(const ScoreImage &im, const unsigned long long *U, float *E, const int32_t *gate, int32_t gate_val, hipStream_t s);
 // xtv_dense.hip: the pass over a dense f64 / f32 matrix or the 16-bit dosage image (h->kind == 1)
 MIH_LOCAL int xtv_dense_device(const mih_mat *h, const XtvWork &w, const double *r_dev, int m, double *out_dev, hipStream_t s);
 

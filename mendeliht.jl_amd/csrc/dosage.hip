@@ -98,11 +98,11 @@ int dosage_alloc(mih_mat *h, int64_t n, int64_t p, int32_t denom, int device)
     h->kind = 1; h->device = device; h->n = n; h->p = p; h->center = h->scale = h->impute = 0;
     h->denom = denom;
     h->du_ld = (n + 7) / 8 * 8;
-    if (hipMalloc((void **)&h->Du, sizeof(uint16_t) * (size_t)h->du_ld * (size_t)p) != hipSuccess) {
+    if (device_malloc((void **)&h->Du, sizeof(uint16_t) * (size_t)h->du_ld * (size_t)p) != hipSuccess) {
         set_error("hipMalloc for the dosage matrix (%lld x %lld u16) failed", (long long)n, (long long)p); (void)hipGetLastError(); return MIH_OOM;
     }
     for (double **a : {&h->mu, &h->sinv, &h->du_mun, &h->du_sc})
-        if (hipMalloc((void **)a, sizeof(double) * (size_t)p) != hipSuccess) { set_error("hipMalloc failed"); (void)hipGetLastError(); return MIH_OOM; }
+        if (device_malloc((void **)a, sizeof(double) * (size_t)p) != hipSuccess) { set_error("hipMalloc failed"); (void)hipGetLastError(); return MIH_OOM; }
     if (hipStreamCreate(&h->stream) != hipSuccess) return MIH_HIP_ERROR;
     return MIH_OK;
 }

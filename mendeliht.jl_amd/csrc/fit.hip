@@ -59,6 +59,7 @@ int mih_session_create(const mih_mat *h, const mih_fit_params *prm, const double
     mih_session_impl *s = new mih_session_impl();
     s->prm = *prm;
     s->next_logl = s->best = -std::numeric_limits<double>::infinity();
+    s->v.long_lived = true;            // the caller steps it for as long as it likes: the automatic rule of the score image applies
     int rc = s->v.create(h, prm, y, z, q);
     if (!rc) rc = s->v.init(train);
     if (rc) { delete s; return rc; }

@@ -82,6 +82,7 @@ struct IhtVar : ShardComm {
     std::vector<uint8_t> zkeep; int64_t zkeepn = 0;
     const double *y_host = nullptr, *z_host = nullptr;
     int init_beta = 0, debias = 0;
+    bool long_lived = false;   // a session (set before create): its set-up may build the matrix's score image (score_image_auto)
     int (*choose_cb)(void *, int32_t, const int64_t *, int64_t, int64_t, int64_t *) = nullptr;   // mih_fit_params::choose
     void *choose_user = nullptr;
     XtvTune tune;                 // how this fit's X'r passes run (mih_fit_params::xtv_digits)

@@ -497,7 +497,7 @@ int IhtVar::create(const mih_mat *hh, const mih_fit_params *prm, const double *y
     MIH_TRY(stage.init(2 * (size_t)kcap + 8));
     MIH_TRY(hpin.alloc((size_t)kcap + kMaxQ + 16, true));
     MIH_TRY(flag.word.alloc(8, true)); flag.word.p[0] = 0; flag.seq = 0;
-    if (!batched) { ArenaScope own_buffers(nullptr); MIH_TRY(xtv_work_init(h, xtv, 1, tune, false)); }     // a few large buffers: their own allocations
+    if (!batched) { ArenaScope own_buffers(nullptr); if (long_lived && xtv_rides_image(h, tune)) score_image_auto(h); MIH_TRY(xtv_work_init(h, xtv, 1, tune, false)); }     // a few large buffers: their own allocations
     MIH_TRY(xv_work_init(h, xv, kcap, kcap - 1024));       // the cache is sized for the model, not for the tie slack of the lists
     MIH_TRY(topk_work_init(topk, kcap));
     if (!(y_shared && z_shared)) {

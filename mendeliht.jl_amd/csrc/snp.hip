@@ -379,9 +379,9 @@ static int finish_missing_ptr(mih_mat *h, const std::vector<int32_t> &cnt, std::
     ptr.assign((size_t)h->p + 1, 0);
     for (int64_t j = 0; j < h->p; ++j) ptr[j + 1] = ptr[j] + cnt[3 * j + 2];
     h->total_missing = ptr[h->p];
-    MIH_HIP(hipMalloc((void **)&h->miss_ptr, sizeof(int64_t) * (size_t)(h->p + 1)));
+    MIH_HIP(device_malloc((void **)&h->miss_ptr, sizeof(int64_t) * (size_t)(h->p + 1)));
     MIH_HIP(hipMemcpy(h->miss_ptr, ptr.data(), sizeof(int64_t) * (size_t)(h->p + 1), hipMemcpyHostToDevice));
-    MIH_HIP(hipMalloc((void **)&h->miss_row, sizeof(int32_t) * (size_t)(h->total_missing > 0 ? h->total_missing : 1)));
+    MIH_HIP(device_malloc((void **)&h->miss_row, sizeof(int32_t) * (size_t)(h->total_missing > 0 ? h->total_missing : 1)));
     return MIH_OK;
 }
 
@@ -414,10 +414,10 @@ int alloc_snp(mih_mat *h)
     h->nbp = (h->n + 127) / 128;
     h->n_pad = h->nbp * 128;
     size_t bytes = sizeof(uint4) * (size_t)h->ncg * (size_t)h->nbp * 64;
-    hipError_t e = hipMalloc((void **)&h->X, bytes);
+    hipError_t e = device_malloc((void **)&h->X, bytes);
     if (e != hipSuccess) { set_error("hipMalloc of %zu bytes for the genotype matrix failed: %s", bytes, hipGetErrorString(e)); return MIH_OOM; }
-    MIH_HIP(hipMalloc((void **)&h->mu, sizeof(double) * (size_t)h->p));
-    MIH_HIP(hipMalloc((void **)&h->sinv, sizeof(double) * (size_t)h->p));
+    MIH_HIP(device_malloc((void **)&h->mu, sizeof(double) * (size_t)h->p));
+    MIH_HIP(device_malloc((void **)&h->sinv, sizeof(double) * (size_t)h->p));
     return MIH_OK;
 }
 
@@ -622,7 +622,7 @@ int mih_snp_create(const uint8_t *bed_cols, int64_t n, int64_t p, int64_t col_st
     } stg;
     for (;;) {                         // a failed allocation degrades to one worker before it fails the create
         const bool ok = hipHostMalloc((void **)&stg.pin, buf_bytes * 2 * nth, hipHostMallocDefault) == hipSuccess &&
-                        hipMalloc((void **)&stg.raw, buf_bytes * 2 * nth) == hipSuccess;
+                        device_malloc((void **)&stg.raw, buf_bytes * 2 * nth) == hipSuccess;
         if (ok) break;
         (void)hipGetLastError();
         if (stg.pin) { (void)hipHostFree(stg.pin); stg.pin = nullptr; }
@@ -830,7 +830,7 @@ int mih_dense_create(const double *x, int64_t n, int64_t p, int device, mih_mat 
     mih_mat *h = new mih_mat();
     h->kind = 1; h->device = device; h->n = n; h->p = p; h->center = h->scale = h->impute = 0;
     auto fail = [&](int code) { mih_mat_destroy(h); return code; };
-    if (hipMalloc((void **)&h->D, sizeof(double) * (size_t)n * (size_t)p) != hipSuccess) { set_error("hipMalloc for dense matrix failed"); (void)hipGetLastError(); return fail(MIH_OOM); }
+    if (device_malloc((void **)&h->D, sizeof(double) * (size_t)n * (size_t)p) != hipSuccess) { set_error("hipMalloc for dense matrix failed"); (void)hipGetLastError(); return fail(MIH_OOM); }
     if (hipMemcpy(h->D, x, sizeof(double) * (size_t)n * (size_t)p, hipMemcpyHostToDevice) != hipSuccess) return fail(MIH_HIP_ERROR);
     if (hipStreamCreate(&h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
     *out = h;
@@ -845,7 +845,7 @@ int mih_dense_create_f32(const float *x, int64_t n, int64_t p, int device, mih_m
     mih_mat *h = new mih_mat();
     h->kind = 1; h->device = device; h->n = n; h->p = p; h->center = h->scale = h->impute = 0;
     auto fail = [&](int code) { mih_mat_destroy(h); return code; };
-    if (hipMalloc((void **)&h->Df, sizeof(float) * (size_t)n * (size_t)p) != hipSuccess) { set_error("hipMalloc for dense matrix failed"); (void)hipGetLastError(); return fail(MIH_OOM); }
+    if (device_malloc((void **)&h->Df, sizeof(float) * (size_t)n * (size_t)p) != hipSuccess) { set_error("hipMalloc for dense matrix failed"); (void)hipGetLastError(); return fail(MIH_OOM); }
     if (hipMemcpy(h->Df, x, sizeof(float) * (size_t)n * (size_t)p, hipMemcpyHostToDevice) != hipSuccess) return fail(MIH_HIP_ERROR);
     if (hipStreamCreate(&h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
     *out = h;
@@ -860,7 +860,7 @@ int mih_dense_create_synthetic(int64_t n, int64_t p, uint64_t seed, int device, 
     mih_mat *h = new mih_mat();
     h->kind = 1; h->device = device; h->n = n; h->p = p; h->center = h->scale = h->impute = 0;
     auto fail = [&](int code) { mih_mat_destroy(h); return code; };
-    if (hipMalloc((void **)&h->D, sizeof(double) * (size_t)n * (size_t)p) != hipSuccess) { set_error("hipMalloc for dense matrix failed"); (void)hipGetLastError(); return fail(MIH_OOM); }
+    if (device_malloc((void **)&h->D, sizeof(double) * (size_t)n * (size_t)p) != hipSuccess) { set_error("hipMalloc for dense matrix failed"); (void)hipGetLastError(); return fail(MIH_OOM); }
     if (hipStreamCreate(&h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
     hipLaunchKernelGGL(k_synth_dense, dim3(8192), dim3(256), 0, h->stream, h->D, n * p, seed);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(MIH_HIP_ERROR);
@@ -872,6 +872,7 @@ int mih_mat_destroy(mih_mat *h)
 {
     if (!h) return MIH_OK;
     (void)hipSetDevice(h->device);
+    score_image_forget(h);
     for (hipStream_t ws : h->worker_streams) if (ws) { (void)hipStreamSynchronize(ws); (void)hipStreamDestroy(ws); }
     h->worker_streams.clear();
     if (h->X) (void)hipFree(h->X);

@@ -763,7 +763,7 @@ static int vcf_stream(mih_vcf *v, int field, int64_t rec0, int64_t nrec, int thr
     } stg;
     for (;;) {                         // a failed allocation degrades to one worker before it fails the create
         if (hipHostMalloc((void **)&stg.pin, per_worker * nth, hipHostMallocDefault) == hipSuccess &&
-            hipMalloc((void **)&stg.dev, per_worker * nth) == hipSuccess) break;
+            device_malloc((void **)&stg.dev, per_worker * nth) == hipSuccess) break;
         (void)hipGetLastError();
         if (stg.pin) { (void)hipHostFree(stg.pin); stg.pin = nullptr; }
         if (stg.dev) { (void)hipFree(stg.dev); stg.dev = nullptr; }

@@ -151,6 +151,43 @@ static int auto_splits(const mih_mat *h, const XtvTune &tn)
     return s;
 }
 
+// the row slices of a pass: the rule above, at least what exact f32 accumulation needs (|g/2 * d/2| <= 1 (base 4) or 4 (base 13)
+// in units of 1/4, so a row slice may hold at most 2^22 / 2^20 rows), at most one per 128-row block and `cap`; -1: too tall
+static int pass_splits(const mih_mat *h, int splits, const DigitMode &dm, int cap)
+{
+    const int64_t need = (h->n_pad + (1ll << dm.rows_log2) - 1) >> dm.rows_log2;
+    if (need > cap) return -1;
+    if (splits < need) splits = (int)need;
+    if (splits > h->nbp) splits = (int)h->nbp;
+    if (splits > cap) splits = cap;
+    return splits;
+}
+int xtv_default_splits(const mih_mat *h, const DigitMode &dm) { return pass_splits(h, auto_splits(h, XtvTune()), dm, kMaxSplits); }
+
+// The single-residual pass over the matrix's score image (score_image.hip) in place of k_xtv_dma<1,2,4,8,fp4>: k_xtv_hom (the
+// digit sums of the one-bit columns' dosage-2 entries), then the class-2 region with the 2-bit kernel's own code and the class-1
+// region with its one-bit variant.  Same row slices, same partial[slice][column]: the finalize kernel is untouched.
+static void launch_xtv_image(const ScoreImage &im, const XtvWork &w, const mih_mat *h, const uint4 *dig, const uint2 *dig2, int64_t dig_stride,
+                             int splits, DigitMode dm, const double *scal, double *partial, hipStream_t s, char *name)
+{
+    constexpr int W = 4, C = 2;
+    launch_xtv_hom(im, w.hom_u.p, w.hom.p, dm.gate, dm.gate_val, s);
+    dm.img_pstride = h->ncg * 32; dm.img_p1 = im.pos1; dm.img_hom = w.hom.p;
+    if (im.ncg2 > 0) {
+        dm.img_col = im.col_of;
+        hipLaunchKernelGGL((k_xtv_dma<1, C, W, 8, false, 0, 1>), dim3((unsigned)((im.ncg2 + W * C - 1) / (W * C) * splits)), dim3(W * 64), 0, s,
+                           reinterpret_cast<const uint4 *>(im.tiles), im.nbp, im.ncg2, dig, dig2, dig_stride, splits, dm, scal, partial);
+    }
+    if (im.nt1 > 0) {
+        dm.img_col = im.col_of + im.ncg2 * 32;
+        // (one tile = two column groups per wave: twice the workgroups of half the length, a shorter tail behind the class-2 launch)
+        hipLaunchKernelGGL((k_xtv_dma<1, 1, W, 8, false, 0, 2>), dim3((unsigned)((im.nt1 + W - 1) / W * splits)), dim3(W * 64), 0, s,
+                           reinterpret_cast<const uint4 *>(im.tiles + (size_t)im.ncg2 * (size_t)im.nbp * 1024), im.nbp, im.nt1, dig, dig2, dig_stride,
+                           splits, dm, scal, partial);
+    }
+    snprintf(name, 48, "k_xtv_dma_img<1,2|1,4,8,fp4>+k_xtv_hom");       // (CT = 2 over the class-2 region | 1 over the class-1 region)
+}
+
 // FP6 digit planes are written in the 16-column layout when the pass runs on the 16x16x128 kernels (always, in the release
 // library; the measurement build also has 32x32x64 shapes)
 static bool xtv_lay16(const DigitMode &dm, const XtvTune &tn)
@@ -187,6 +224,20 @@ static void choose_mode(const mih_mat *h, const XtvTune &tn, bool batched, Digit
         else if (tn.variant >= 0 || h->n_pad > ((int64_t)kMaxSplits << dm.rows_log2)) digit_mode(1316, dm);
         if (h->n_pad > ((int64_t)kMaxSplits << dm.rows_log2)) digit_mode(428, dm);
     }
+}
+
+// the pass the score image serves: the 428 format on the product's kernel and row slices (xtv_work_init pins an image on this condition,
+// the automatic rule builds one on it)
+static bool image_pass(const DigitMode &dm, const XtvTune &tn)
+{
+    return dm.base == 4 && tn.variant < 0 && tn.multi_variant == 0 && tn.slices == 0;
+}
+bool xtv_rides_image(const mih_mat *h, const XtvTune &tn)        // ... for the workspace of a single fit (batched = false)
+{
+    if (h->kind != 0 || !xtv_digits_valid(tn.digits)) return false;
+    DigitMode dm;
+    choose_mode(h, tn, false, dm);
+    return image_pass(dm, tn);
 }
 
 int xtv_lockstep_width(const mih_mat *h, const XtvTune &tn)
@@ -231,6 +282,15 @@ int xtv_work_init(const mih_mat *h, XtvWork &w, int m, const XtvTune &tune, bool
     MIH_HIP(hipMemsetAsync(w.scal.p, 0, sizeof(double) * rhs_cap * 4, h->stream));
     MIH_HIP(hipStreamSynchronize(h->stream));
     w.m_cap = m; w.splits_cap = kMaxSplits;
+    // a single-residual workspace in the 428 format rides the matrix's score image if it has one now, and pins it
+    w.img.reset();
+    if (m == 1 && image_pass(w.dm, tune)) {
+        std::shared_ptr<const ScoreImage> im = score_image_of(h);
+        if (im && im->nbp == h->nbp) {
+            if (w.hom_u.alloc((size_t)h->n_pad) == MIH_OK && w.hom.alloc(std::max<size_t>((size_t)im->splits * (size_t)im->pos1 * 32, 1)) == MIH_OK) w.img = im;
+            else { w.hom_u.release(); w.hom.release(); }          // no room for the scratch: the 2-bit pass
+        }
+    }
     return MIH_OK;
 }
 
@@ -293,16 +353,16 @@ int xtv_device(const mih_mat *h, XtvWork &w, const double *r_dev, int m, double 
     if (h->kind == 1) return xtv_dense_device(h, w, r_dev, m, out_dev, s);
     if (m > w.m_cap) { set_error("X'r workspace too small"); return MIH_BAD_ARG; }
     int splits = probe_splits(tn);
+    const bool own_splits = splits > 0;
     if (splits <= 0) splits = auto_splits(h, tn);
-    // exactness of the f32 accumulators: |g/2 * d/2| <= 1 (base 4) or 4 (base 13) in units of 1/4, so a row
-    // slice may hold at most 2^22 / 2^20 rows
     DigitMode dm = (w.use_alt && w.has_alt) ? w.dm_alt : w.dm;
     dm.lay16 = xtv_lay16(dm, tn);
-    const int64_t need = (h->n_pad + (1ll << dm.rows_log2) - 1) >> dm.rows_log2;
-    if (need > w.splits_cap) { set_error("n = %lld rows needs more than %d row slices for exact accumulation", (long long)h->n, w.splits_cap); return MIH_BAD_DIM; }
-    if (splits < need) splits = (int)need;
-    if (splits > h->nbp) splits = (int)h->nbp;
-    if (splits > w.splits_cap) splits = w.splits_cap;
+    splits = pass_splits(h, splits, dm, w.splits_cap);
+    if (splits < 0) { set_error("n = %lld rows needs more than %d row slices for exact accumulation", (long long)h->n, w.splits_cap); return MIH_BAD_DIM; }
+    // the score image serves this call if the workspace pinned one and the pass is the library-default single-residual one on the
+    // image's own row slices (otherwise the bits would differ)
+    const ScoreImage *img = (w.img && m == 1 && dm.base == 4 && !own_splits && splits == w.img->splits) ? w.img.get() : nullptr;
+    if (img) dm.hom_u = w.hom_u.p;
     const int64_t nblk = h->nbp * 2, pstride = h->ncg * 32;
     double *part = w.scal.p + w.rhs_cap * 4;
     dm.gate = w.gate; dm.gate_val = w.gate_val;
@@ -331,8 +391,10 @@ int xtv_device(const mih_mat *h, XtvWork &w, const double *r_dev, int m, double 
         double *partial = w.partial.p + (int64_t)ps.u0 * splits * pstride;
         PassRecord rec;
         const bool prof = prof_begin(h, s, rec);
-        const int rc = dispatch_xtv(tn, ps.nr, ps.half, h, dig_all + (int64_t)ps.t * nblk * 64, dig2_all + (int64_t)ps.t * nblk * 64, nblk * 64,
-                                    splits, dq, w.scal.p + 4 * ps.u0, partial, s, rec.kernel);
+        int rc = MIH_OK;
+        if (img && ps.nr == 1) launch_xtv_image(*img, w, h, dig_all, dig2_all, nblk * 64, splits, dq, w.scal.p, partial, s, rec.kernel);
+        else rc = dispatch_xtv(tn, ps.nr, ps.half, h, dig_all + (int64_t)ps.t * nblk * 64, dig2_all + (int64_t)ps.t * nblk * 64, nblk * 64,
+                               splits, dq, w.scal.p + 4 * ps.u0, partial, s, rec.kernel);
         if (prof) {
             rec.residuals = ps.u1 - ps.u0; rec.operands = ps.nr; rec.stream_tag = w.stream_tag;
             prof_end(h, s, rec);

@@ -155,6 +155,7 @@ k_digits(const double *__restrict__ r, int64_t n, int64_t nblk, int m, DigitMode
             // loop below produces -- and the FP4 (e2m1) code of d_t / 2 is a four-entry table: u = 0 -> -1.0 (1010), 1 -> -0.5 (1001),
             // 2 -> 0, 3 -> +0.5 (0001).  No loop-carried dependency.
             const unsigned long long U = (unsigned long long)R + 0x00AAAAAAAAAAAAAAull;
+            if (dm.hom_u && vs == 0) dm.hom_u[i] = U;        // a pass over the score image follows: k_xtv_hom sums these digits (a peeled or pad row: all d_t = 0)
             for (int t = 0; t < dm.ndig; ++t) {
                 const uint32_t u = (uint32_t)(U >> (2 * t)) & 3u;
                 const uint32_t code = (0x109Au >> (4u * u)) & 15u;

@@ -489,7 +489,45 @@ __device__ __forceinline__ void xtv_epilogue_lds(const f32x16 (&acc)[CT][NR], fl
     else xtv_epilogue_lds_s<CT, NR, 32>(acc, buf, lane, cg0, ncg, split, splits, dm, scal, partial);
 }
 
-template <int NR, int CT, int WAVES, int D, bool FP6, int MODE = 0>      // MODE 1: no MFMAs, 2: no copies after the prologue (timing probes only)
+// Epilogue of the passes over the score image (score_image.hip; one residual, 28 base-4 digit columns in 32 slots).  The wave's
+// column groups g0 .. g0 + ACT - 1 of its region (ng groups) sit at image positions; dm.img_col maps a position to its column of
+// the matrix and the dot product goes where the 2-bit pass puts it.  ONEBIT: the tile was multiplied as the plane [g >= 1], so a
+// dosage-2 entry is short by (1/2)(d_t / 2): 0.25 * (sum of d_t over the column's dosage-2 rows of the slice, k_xtv_hom) is added to
+// digit column t first.  The total is the 2-bit pass's S_t, below 2^24 quarter units: the f32 addition is exact, and the
+// recombination sees the 2-bit pass's numbers in its order (xtv_epilogue_lds_s<.., 32>).
+template <int ACT, bool ONEBIT>
+__device__ __forceinline__ void xtv_epilogue_img(f32x16 (&acc)[ACT][1], float *buf, int lane, int64_t g0, int64_t ng, int split,
+                                                 DigitMode dm, const double *__restrict__ scal, double *__restrict__ partial)
+{
+    const int col = lane & 31, hi = lane >> 5;
+    double wgt[32];
+    digit_weights<32>(wgt, 4, 4u, dm.ndig);
+    #pragma unroll
+    for (int c = 0; c < ACT; ++c) {
+        const int64_t g = g0 + c;
+        if (ONEBIT && g < ng) {
+            const float *e = dm.img_hom + ((int64_t)split * dm.img_p1 + g * 32) * 32 + col;
+            #pragma unroll
+            for (int q = 0; q < 16; ++q) acc[c][0][q] += 0.25f * e[((q & 3) + 8 * (q >> 2) + 4 * hi) * 32];
+        }
+        __builtin_amdgcn_wave_barrier();
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+            *reinterpret_cast<f32x4v *>(buf + col * kTileRS + 8 * q + 4 * hi) =
+                f32x4v{acc[c][0][4 * q], acc[c][0][4 * q + 1], acc[c][0][4 * q + 2], acc[c][0][4 * q + 3]};
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 32 && g < ng) {
+            const int64_t j = dm.img_col[g * 32 + lane];
+            if (j >= 0) partial[(int64_t)split * dm.img_pstride + j] = digit_sum<32>(buf + lane, wgt) * scal[1];
+        }
+    }
+}
+
+// IMG (the score image, score_image.hip; one FP4 operand): 1 -- X is the image's class-2 region, the matrix's own tile format,
+// and only the epilogue differs (the column map); 2 -- X is the class-1 region: a 1 KB tile holds TWO column groups at one bit per
+// genotype, a lane's dwords 0, 1 the row halves of group A and 2, 3 those of group B, so a wave owns 2 CT groups (ACT) and runs four
+// MFMAs per tile and step.  The feed, the wait counts and the barrier are the same.
+template <int NR, int CT, int WAVES, int D, bool FP6, int MODE = 0, int IMG = 0>      // MODE 1: no MFMAs, 2: no copies after the prologue (timing probes only)
 __global__ void __launch_bounds__(WAVES * 64, 1)
 k_xtv_dma(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg, const uint4 *__restrict__ dig, const uint2 *__restrict__ dig2,
           int64_t dig_stride, int splits, DigitMode dm, const double *__restrict__ scal,
@@ -502,15 +540,17 @@ k_xtv_dma(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg, const uint4 *__
     static_assert(S * STAGE <= 160 * 1024, "LDS ring too large");
     static_assert(D * L <= 63, "vmcnt range");
     static_assert(S * STAGE >= WAVES * 32 * 36 * 4, "the epilogue buffers overlay the ring");
+    static_assert(IMG == 0 || (NR == 1 && !FP6 && MODE == 0), "the score image serves the single-residual FP4 pass");
+    constexpr int ACT = IMG == 2 ? 2 * CT : CT;     // column groups (accumulator tiles) of a wave
     if (dm.gate && *dm.gate != dm.gate_val) return;      // (uniform: one scalar load and a branch in front of everything)
     __shared__ uint4 lds[S * STAGE / 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const RowSlice sl = row_slice<WAVES, CT>(splits, nbp, wave);
 
-    f32x16 acc[CT][NR];
+    f32x16 acc[ACT][NR];
     #pragma unroll
-    for (int c = 0; c < CT; ++c)
+    for (int c = 0; c < ACT; ++c)
         #pragma unroll
         for (int v = 0; v < NR; ++v)
             #pragma unroll
@@ -524,20 +564,31 @@ k_xtv_dma(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg, const uint4 *__
             #pragma unroll
             for (int c = 0; c < CT; ++c) raw[c] = *reinterpret_cast<const i32x4v *>(feed.ldsb + st * STAGE + feed.mydos + c * 1024 + lane * 16);
         };
-        auto expand = [&](const i32x4v (&raw)[CT], i32x4v (&a)[CT][2]) {
-            const int M = 0x33333333 & sl.amask;
-            #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const unsigned x = raw[c][0], y = raw[c][1], z = raw[c][2], w = raw[c][3];
-                a[c][0] = i32x4v{(int)x & M, (int)(x >> 2) & M, (int)y & M, (int)(y >> 2) & M};
-                a[c][1] = i32x4v{(int)z & M, (int)(z >> 2) & M, (int)w & M, (int)(w >> 2) & M};
+        auto expand = [&](const i32x4v (&raw)[CT], i32x4v (&a)[ACT][2]) {
+            if constexpr (IMG == 2) {       // dword 2 g + e: group g, row half e; element 8k + q at bit 4q + k (nibble 0001 = FP4 0.5)
+                const int M = 0x11111111 & sl.amask;
+                #pragma unroll
+                for (int c = 0; c < CT; ++c)
+                    #pragma unroll
+                    for (int ge = 0; ge < 4; ++ge) {
+                        const unsigned u = raw[c][ge];
+                        a[2 * c + (ge >> 1)][ge & 1] = i32x4v{(int)u & M, (int)(u >> 1) & M, (int)(u >> 2) & M, (int)(u >> 3) & M};
+                    }
+            } else {
+                const int M = 0x33333333 & sl.amask;
+                #pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    const unsigned x = raw[c][0], y = raw[c][1], z = raw[c][2], w = raw[c][3];
+                    a[c][0] = i32x4v{(int)x & M, (int)(x >> 2) & M, (int)y & M, (int)(y >> 2) & M};
+                    a[c][1] = i32x4v{(int)z & M, (int)(z >> 2) & M, (int)w & M, (int)(w >> 2) & M};
+                }
             }
         };
 
         #pragma unroll
         for (int s = 0; s < D; ++s) feed.issue(s, s);
         i32x4v araw[CT];
-        i32x4v A[2][CT][2];
+        i32x4v A[2][ACT][2];
         i32x8 B[2];
         wait_vm_barrier<(D - 1) * L>();
         read_dos(0, araw);
@@ -548,7 +599,7 @@ k_xtv_dma(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg, const uint4 *__
 #define MIH_MM(a_, b_, c_) (MODE == 1 ? fake4x(a_, b_, c_) : mfma4x<FP6>(a_, b_, c_))
 #define MIH_DMA_ITEM(P, I, BB)                                                                                     \
             _Pragma("unroll")                                                                                      \
-            for (int c = 0; c < CT; ++c) acc[c][(I) >> 1] = MIH_MM(A[P][c][(I) & 1], BB, acc[c][(I) >> 1]);
+            for (int c = 0; c < ACT; ++c) acc[c][(I) >> 1] = MIH_MM(A[P][c][(I) & 1], BB, acc[c][(I) >> 1]);
 #define MIH_ALL(i_) true
         for (int t = 0; t < nb; t += 2) {
             MIH_RING_STEP(0, t, MODE != 2, MIH_ALL, MIH_DMA_ITEM)
@@ -560,7 +611,10 @@ k_xtv_dma(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg, const uint4 *__
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the look-ahead copies have landed, every wave is done with the ring
     }
     if (sl.cg0 >= ncg) return;
-    xtv_epilogue_lds<CT, NR>(acc, reinterpret_cast<float *>(lds) + wave * (32 * 36), lane, sl.cg0, ncg, sl.split, splits, dm, scal, partial);
+    float *buf = reinterpret_cast<float *>(lds) + wave * (32 * 36);
+    if constexpr (IMG == 1) xtv_epilogue_img<ACT, false>(acc, buf, lane, sl.cg0, ncg, sl.split, dm, scal, partial);
+    else if constexpr (IMG == 2) xtv_epilogue_img<ACT, true>(acc, buf, lane, 2 * sl.cg0, dm.img_p1 / 32, sl.split, dm, scal, partial);
+    else xtv_epilogue_lds<CT, NR>(acc, buf, lane, sl.cg0, ncg, sl.split, splits, dm, scal, partial);
 }
 
 // The same pass on v_mfma_f32_16x16x128_f8f6f4.  Under the package power cap the chip holds a higher clock on the
