@@ -523,8 +523,9 @@ struct ScoreImage {
     int64_t pos1 = 0;                          // class-1 positions = 2 * nt1 * 32
     char *tiles = nullptr;                     // ncg2 * nbp KB in the matrix's tile format, then nt1 * nbp KB of one-bit tiles
     int32_t *col_of = nullptr;                 // image position -> column of the matrix (-1: pad); class 2 first
-    uint32_t *seg_off = nullptr;               // [(slice * pos1 + class-1 position) * nss + sub-slice], + 1 : a list's start, in 8 entries
-    uint16_t *rows = nullptr;                  // the lists: row numbers inside the sub-slice, ascending, padded to 8 entries
+    uint32_t *seg_off = nullptr;               // [((slice * pos1 / 64 + slot group) * nss + sub-slice) * 64 + lane], + 1 : running chunk count
+    uint16_t *rows = nullptr;                  // the lists: row numbers inside the sub-slice, ascending, padded to chunks of 8 entries; the chunks
+                                               // of one (slice, slot group, sub-slice) share a block, chunk-index-major (hom_chunk_slot, score_image.h)
     int32_t *order = nullptr;                  // [pos1] : class-1 positions by falling number of dosage-2 entries (k_xtv_hom's threads)
     size_t bytes = 0;
     ~ScoreImage();

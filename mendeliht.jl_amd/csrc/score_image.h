@@ -102,4 +102,26 @@ struct HomSum {
 };
 MIH_HD uint64_t hom_u(long long R) { return (uint64_t)R + 0x00AAAAAAAAAAAAAAull; }
 
+// Where the 16-byte chunks of a slot group's lists live.  A slot group is the 64 consecutive slots one wave of k_xtv_hom owns; per
+// (slice, group, sub-slice) its lists share one block of sum cnt[] chunks, chunk-index-major and compacted: chunk 0 of every
+// lane that has one, in lane order, then chunk 1 of every lane that has two, ...  A wave's load of its chunks c is then one
+// contiguous run.  cnt: the 64 lanes' chunk counts; the results are relative to the block's first chunk.
+constexpr int kHomGroup = 64;
+// first place of the chunks of index c: sum of min(cnt[l], c)
+MIH_HD uint32_t hom_chunk_base(const uint32_t *cnt, uint32_t c)
+{
+    uint32_t s = 0;
+    for (int l = 0; l < kHomGroup; ++l) s += cnt[l] < c ? cnt[l] : c;
+    return s;
+}
+// the lane's place among them: the lower lanes whose list is longer than c chunks (the kernel: one ballot, one masked bit count)
+MIH_HD uint32_t hom_chunk_rank(const uint32_t *cnt, int lane, uint32_t c)
+{
+    uint32_t r = 0;
+    for (int l = 0; l < lane; ++l) r += cnt[l] > c ? 1u : 0u;
+    return r;
+}
+// place of chunk c < cnt[lane] of the lane's list
+MIH_HD uint32_t hom_chunk_slot(const uint32_t *cnt, int lane, uint32_t c) { return hom_chunk_base(cnt, c) + hom_chunk_rank(cnt, lane, c); }
+
 }  // namespace mih

@@ -133,23 +133,38 @@ k_img_pack(const uint4 *__restrict__ X, int64_t nbp, int64_t ncg2, const int32_t
 }
 
 // The dosage-2 rows of one (sub-slice, class-1 position): FILL = false counts them, FILL = true writes them, ascending, as row
-// numbers inside the sub-slice and pads the list to a multiple of 8 entries with the number one past a sub-slice's last row.  Thread = one list.
+// numbers inside the sub-slice and pads the list to a multiple of 8 entries with the number one past a sub-slice's last row.
+// Thread = one list, by slot (position through `order`): a wave is a slot group of k_xtv_hom, the lists of one (slice, group,
+// sub-slice) share a block of chunks and a list's chunk c goes to hom_chunk_slot() of the group's 64 chunk counts (score_image.h).
+// The reads of X are scattered (the slots of a group are columns from all over the matrix): build time.
+MIH_HD int64_t hom_seg(int split, int64_t pos1, int64_t slot, int nss, int k)      // seg_off's index of a list: (slice, group, sub-slice, lane)
+{
+    return (((int64_t)split * (pos1 / kHomGroup) + slot / kHomGroup) * nss + k) * kHomGroup + slot % kHomGroup;
+}
 template <bool FILL>
 __global__ void __launch_bounds__(256)
 k_img_lists(const uint4 *__restrict__ X, int64_t nbp, int splits, int nss, int64_t pos1, const int32_t *__restrict__ col1,
-            uint32_t *__restrict__ count, const uint32_t *__restrict__ seg_off, uint16_t *__restrict__ rows)
+            const int32_t *__restrict__ order, uint32_t *__restrict__ count, const uint32_t *__restrict__ seg_off, uint16_t *__restrict__ rows)
 {
-    const int64_t pos = blockIdx.x * 256ll + threadIdx.x;
-    if (pos >= pos1) return;
+    __shared__ uint32_t chunks[4][kHomGroup];
+    const int64_t slot = blockIdx.x * 256ll + threadIdx.x;
+    const bool live = slot < pos1;                       // (pos1 is a multiple of 64: whole waves)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = blockIdx.y;                          // slice * nss + sub-slice of it
     const int split = sub / nss, k = sub - split * nss;
     const int64_t bps = (nbp + splits - 1) / splits;
     const int64_t s1 = std::min<int64_t>((int64_t)(split + 1) * bps, nbp);
     const int64_t b0 = split * bps + (int64_t)k * kHomSubBlocks, b1 = std::min<int64_t>(b0 + kHomSubBlocks, s1);
-    const int64_t seg = ((int64_t)split * pos1 + pos) * nss + k;       // the lists of a (slice, position) follow each other
-    const int64_t j = col1[pos];
+    const int64_t seg = live ? hom_seg(split, pos1, slot, nss, k) : 0;
+    if (FILL) {
+        chunks[wave][lane] = live ? seg_off[seg + 1] - seg_off[seg] : 0u;
+        __syncthreads();
+    }
+    if (!live) return;
+    const int64_t j = col1[order[slot]];
     uint32_t cnt = 0;
-    uint16_t *dst = FILL ? rows + (size_t)seg_off[seg] * 8 : nullptr;
+    const uint32_t *gc = chunks[wave];
+    uint16_t *blk = FILL ? rows + (size_t)seg_off[seg - lane] * 8 : nullptr, *dst = blk;      // the group's block; the list's current chunk
     if (j >= 0) {
         const uint4 *q = X + (j >> 5) * nbp * 64 + (j & 31);
         for (int64_t b = b0; b < b1; ++b) {
@@ -163,7 +178,8 @@ k_img_lists(const uint4 *__restrict__ X, int64_t nbp, int splits, int nss, int64
                 else
                     while (hi) {
                         const int bit = __ffs(hi) - 1;
-                        dst[cnt++] = (uint16_t)((b - b0) * 128 + 16 * i + (bit >> 1));
+                        if ((cnt & 7u) == 0) dst = blk + (size_t)hom_chunk_slot(gc, lane, cnt >> 3) * 8;
+                        dst[cnt++ & 7u] = (uint16_t)((b - b0) * 128 + 16 * i + (bit >> 1));
                         hi &= hi - 1;
                     }
             }
@@ -171,13 +187,14 @@ k_img_lists(const uint4 *__restrict__ X, int64_t nbp, int splits, int nss, int64
     }
     if (!FILL) count[seg] = cnt;
     else
-        while (cnt & 7u) dst[cnt++] = (uint16_t)(kHomSubBlocks * 128);      // padding: the slot behind the sub-slice's rows (U of R = 0)
+        while (cnt & 7u) dst[cnt++ & 7u] = (uint16_t)(kHomSubBlocks * 128);   // padding: the slot behind the sub-slice's rows (U of R = 0)
 }
 
 // ---- the exception kernel ---------------------------------------------------------------------------------------------------
 // E[slice][class-1 position][t] = sum of digit t of R over the position's dosage-2 rows in the slice.  A workgroup takes 512
 // positions of one row slice and walks the slice's sub-slices: U of the sub-slice's rows goes to LDS once, every thread then
-// follows its own list (16 B = 8 row numbers a load) and adds up the 2-bit fields of U[row] in SWAR form (HomSum).  Integer sums:
+// follows its own list (16 B = 8 row numbers a load; the loads of a wave are one contiguous run of the group's block, and the
+// next one is in flight while this one is added) and adds up the 2-bit fields of U[row] in SWAR form (HomSum).  Integer sums:
 // no order to keep.  Runs between k_digits and the pass, under the same gate.
 constexpr int kHomThreads = 512;
 __global__ void __launch_bounds__(kHomThreads)
@@ -187,7 +204,7 @@ k_xtv_hom(const unsigned long long *__restrict__ U, int64_t nbp, int splits, int
 {
     if (gate && *gate != gate_val) return;
     constexpr int SUB = kHomSubBlocks * 128;
-    __shared__ unsigned long long su[SUB + 1];            // [SUB]: what a padding entry reads: U of R = 0
+    __shared__ __align__(16) unsigned long long su[SUB + 2];      // [SUB]: what a padding entry reads: U of R = 0
     const int split = blockIdx.x % splits;
     // thread -> position through `order`: the positions by falling number of dosage-2 entries, so that the lanes of a wave walk
     // lists of about the same length and the long lists start first (of every slice: the slice is the fast grid index)
@@ -198,28 +215,74 @@ k_xtv_hom(const unsigned long long *__restrict__ U, int64_t nbp, int splits, int
     HomSum hs;
     hs.init();
     if (threadIdx.x == 0) su[SUB] = hom_u(0);
-    // the thread's lists of this slice are one run of 16-byte chunks from `cur` on
+    // The wave is one slot group (kHomGroup = 64 = the wave; pos1 is a multiple of 64, so a wave is live or not as a whole).  Its
+    // offsets of a sub-slice are 64 consecutive entries of seg_off: a lane's chunk count is the difference to its successor's
+    // entry (lane 63: lane 0's of the next sub-slice), the block of the group's chunks starts at lane 0's.  Chunk c of the lane
+    // is at base_c + (lower lanes with more than c chunks), base_c+1 = base_c + (lanes with more than c chunks): hom_chunk_slot()
+    // of score_image.h by ballots.  The wave's load of its chunks c is one contiguous run.
     const uint4 *all = reinterpret_cast<const uint4 *>(rows);
-    const uint32_t *off = seg_off + (pos < pos1 ? ((int64_t)split * pos1 + pos) * nss : 0);
-    uint32_t cur = pos < pos1 ? off[0] : 0u;
+    const int lane = threadIdx.x & 63;
+    const bool live = slot < pos1;
+    const uint32_t *off = seg_off + (live ? hom_seg(split, pos1, slot - lane, nss, 0) : 0);
+    uint32_t o_cur = live ? off[lane] : 0u;
+    // U of a sub-slice goes through registers, 16 bytes a thread and round, every round's load in flight at once (one load, one wait,
+    // one LDS write per round cost sixteen trips to the L2 between the two barriers), and the NEXT sub-slice's loads are issued
+    // before this one's lists are walked.  (A macro, not a lambda: captured by a lambda, st[] went to scratch memory.)
+    constexpr int kStage = SUB / (2 * kHomThreads);
+    static_assert(SUB % (2 * kHomThreads) == 0, "a sub-slice is a whole number of 16-byte rounds of the workgroup");
+    const ulonglong2 *U2 = reinterpret_cast<const ulonglong2 *>(U);
+    ulonglong2 st[kStage];
+#define MIH_HOM_FETCH(k_)                                                                                               \
+    {   /* (past the slice's end: nothing is read) */                                                                    \
+        const int64_t fb0 = s0 + (int64_t)(k_) * kHomSubBlocks, fb1 = std::min<int64_t>(fb0 + kHomSubBlocks, s1);         \
+        const int len2 = (int)(fb1 - fb0) * 64;                                                                          \
+        _Pragma("unroll")                                                                                                \
+        for (int j = 0; j < kStage; ++j) {                                                                               \
+            const int i = j * kHomThreads + (int)threadIdx.x;                                                            \
+            st[j] = i < len2 ? U2[fb0 * 64 + i] : make_ulonglong2(0, 0);                                                 \
+        }                                                                                                                \
+    }
+    MIH_HOM_FETCH(0)
     for (int k = 0; k < nss; ++k) {
         const int64_t b0 = s0 + (int64_t)k * kHomSubBlocks, b1 = std::min<int64_t>(b0 + kHomSubBlocks, s1);
         if (b0 >= b1) break;                              // (uniform)
         const int len = (int)(b1 - b0) * 128;
+        // the next sub-slice's offsets, requested before the barrier (behind the group's last sub-slice only lane 0's entry
+        // exists for certain: it is seg_off's last)
+        const uint32_t o_nxt = live ? off[(k + 1) * kHomGroup + (k + 1 < nss ? lane : 0)] : 0u;
         __syncthreads();
-        for (int i = threadIdx.x; i < len; i += kHomThreads) su[i] = U[b0 * 128 + i];
+        #pragma unroll
+        for (int j = 0; j < kStage; ++j) {
+            const int i = j * kHomThreads + (int)threadIdx.x;
+            if (2 * i < len) reinterpret_cast<ulonglong2 *>(su)[i] = st[j];
+        }
         __syncthreads();
-        if (pos < pos1) {
-            const uint32_t o1 = off[k + 1];
-            for (; cur < o1; ++cur) {
-                const uint4 v = all[cur];
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                uint64_t u8[kHomChunk];
-                #pragma unroll
-                for (int i = 0; i < kHomChunk; ++i) u8[i] = su[(w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu];
-                hs.add_chunk(u8);                                              // (folds and flushes at its own cadence, score_image.h)
+        if (k + 1 < nss) MIH_HOM_FETCH(k + 1)
+        if (live) {
+            const uint32_t up = (uint32_t)__shfl_down((int)o_cur, 1);
+            const uint32_t nxt0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)o_nxt);      // (by the whole wave: not inside the select)
+            const uint32_t cnt = (lane == 63 ? nxt0 : up) - o_cur;
+            uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)o_cur);
+            uint64_t m = __ballot(cnt > 0u);
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (cnt > 0u) v = all[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))];
+            for (uint32_t c = 0; m != 0; ++c) {           // (wave-uniform: as many rounds as the longest list has chunks)
+                base += (uint32_t)__popcll(m);
+                const uint64_t m1 = __ballot(cnt > c + 1u);
+                uint4 vn = v;                             // chunk c + 1 is on its way while chunk c is gathered and added
+                if (cnt > c + 1u) vn = all[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u))];
+                if (cnt > c) {
+                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                    uint64_t u8[kHomChunk];
+                    #pragma unroll
+                    for (int i = 0; i < kHomChunk; ++i) u8[i] = su[(w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu];
+                    hs.add_chunk(u8);                                          // (folds and flushes at its own cadence, score_image.h)
+                }
+                v = vn;
+                m = m1;
             }
         }
+        o_cur = o_nxt;
     }
     if (pos >= pos1) return;
     hs.flush();
@@ -234,6 +297,7 @@ k_xtv_hom(const unsigned long long *__restrict__ U, int64_t nbp, int splits, int
         reinterpret_cast<float4 *>(e)[q] = f;
     }
 }
+#undef MIH_HOM_FETCH
 
 void launch_xtv_hom(const ScoreImage &im, const unsigned long long *U, float *E, const int32_t *gate, int32_t gate_val, hipStream_t s)
 {
@@ -243,11 +307,29 @@ void launch_xtv_hom(const ScoreImage &im, const unsigned long long *U, float *E,
 }
 
 // The library's default threshold: a column is class 1 if at most this fraction of its entries is a dosage 2
-// (profiles/score_image.md: the sweep it comes from).
-constexpr double kDefaultHomFraction = 0.01;
+// (profiles/score_image.md §9: the sweep it comes from; 0.015 .. 0.025 are within its noise of each other).
+constexpr double kDefaultHomFraction = 0.02;
 
 // classification: c2 of every column on the host, the image's positions, and what the image would weigh
-struct ImagePlan { std::vector<int32_t> col_of, order; int64_t ncg2 = 0, nt1 = 0, p1 = 0; size_t tile_bytes = 0; };
+struct ImagePlan { std::vector<int32_t> col_of, order; int64_t ncg2 = 0, nt1 = 0, p1 = 0, hom_entries = 0; size_t tile_bytes = 0; };
+// the image's row slices (those of the library's default pass) and the sub-slices of one; false: the matrix is too tall for the pass
+static bool image_slices(const mih_mat *h, int &splits, int &nss)
+{
+    DigitMode dm = {4, 28, 1, 32, 53, 22};
+    splits = xtv_default_splits(h, dm);
+    if (splits <= 0) return false;
+    const int64_t bps = (h->nbp + splits - 1) / splits;
+    nss = (int)((bps + kHomSubBlocks - 1) / kHomSubBlocks);
+    return true;
+}
+// an upper bound of what the lists and their offset table weigh: 2 bytes an entry, at most 14 bytes of padding a list
+static size_t plan_list_bytes(const mih_mat *h, const ImagePlan &pl)
+{
+    int splits = 0, nss = 0;
+    if (!image_slices(h, splits, nss)) return 0;
+    const size_t nseg = (size_t)splits * (size_t)nss * (size_t)pl.nt1 * 64;
+    return 2 * (size_t)pl.hom_entries + 14 * nseg + sizeof(uint32_t) * (nseg + 1);
+}
 static int plan_image(const mih_mat *h, double tau, ImagePlan &pl)
 {
     if (h->p >= (1ll << 31)) { set_error("the score image needs p < 2^31"); return MIH_BAD_DIM; }       // (its column maps are int32)
@@ -261,6 +343,8 @@ static int plan_image(const mih_mat *h, double tau, ImagePlan &pl)
     std::vector<int32_t> one, two;
     for (int64_t j = 0; j < h->p; ++j) ((double)hc[(size_t)j] <= lim ? one : two).push_back((int32_t)j);
     pl.p1 = (int64_t)one.size();
+    pl.hom_entries = 0;
+    for (int32_t j : one) pl.hom_entries += hc[(size_t)j];
     pl.ncg2 = ((int64_t)two.size() + 31) / 32;
     pl.nt1 = (pl.p1 + 63) / 64;
     pl.col_of.assign((size_t)(pl.ncg2 + 2 * pl.nt1) * 32, -1);
@@ -282,11 +366,7 @@ static int build_image(const mih_mat *h, double tau, const ImagePlan &pl, std::s
     std::shared_ptr<ScoreImage> im(new ScoreImage());
     im->device = h->device; im->tau = tau; im->nbp = h->nbp;
     im->ncg2 = pl.ncg2; im->nt1 = pl.nt1; im->p1 = pl.p1; im->pos1 = 2 * pl.nt1 * 32;
-    DigitMode dm = {4, 28, 1, 32, 53, 22};
-    im->splits = xtv_default_splits(h, dm);
-    if (im->splits <= 0) { set_error("the matrix is too tall for the single-residual pass"); return MIH_BAD_DIM; }
-    const int64_t bps = (h->nbp + im->splits - 1) / im->splits;
-    im->nss = (int)((bps + kHomSubBlocks - 1) / kHomSubBlocks);
+    if (!image_slices(h, im->splits, im->nss)) { set_error("the matrix is too tall for the single-residual pass"); return MIH_BAD_DIM; }
     hipStream_t s = h->stream;
     auto oom = [&](const char *what) { (void)hipGetLastError(); set_error("no device memory for the score image (%s)", what); return MIH_OOM; };
     if (device_malloc(&im->tiles, std::max<size_t>(pl.tile_bytes, 1024)) != hipSuccess) return oom("tiles");
@@ -308,7 +388,7 @@ static int build_image(const mih_mat *h, double tau, const ImagePlan &pl, std::s
         const dim3 grid((unsigned)((im->pos1 + 255) / 256), (unsigned)(im->splits * im->nss));
         const int32_t *col1 = im->col_of + pl.ncg2 * 32;
         hipLaunchKernelGGL(k_img_lists<false>, grid, dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X), h->nbp, im->splits, im->nss, im->pos1, col1,
-                           cnt.p, (const uint32_t *)nullptr, (uint16_t *)nullptr);
+                           im->order, cnt.p, (const uint32_t *)nullptr, (uint16_t *)nullptr);
         std::vector<uint32_t> hc(nseg + 1);
         MIH_HIP(hipMemcpyAsync(hc.data(), cnt.p, sizeof(uint32_t) * nseg, hipMemcpyDeviceToHost, s));
         MIH_HIP(hipStreamSynchronize(s));
@@ -320,7 +400,7 @@ static int build_image(const mih_mat *h, double tau, const ImagePlan &pl, std::s
         if (device_malloc(&im->rows, list_bytes) != hipSuccess) return oom("lists");
         MIH_HIP(hipMemcpyAsync(im->seg_off, hc.data(), sizeof(uint32_t) * (nseg + 1), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_img_lists<true>, grid, dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X), h->nbp, im->splits, im->nss, im->pos1, col1,
-                           (uint32_t *)nullptr, im->seg_off, im->rows);
+                           im->order, (uint32_t *)nullptr, im->seg_off, im->rows);
         MIH_HIP(hipStreamSynchronize(s));
     } else {
         const uint32_t z = 0;
@@ -335,7 +415,8 @@ static int build_image(const mih_mat *h, double tau, const ImagePlan &pl, std::s
 
 // The automatic rule (set-up of a session whose workspace will ride the image -- xtv_rides_image; never inside a step): a 2-bit matrix of
 // 4 GiB or more (the reserve rule's size) gets an image if the image's tiles are at most 0.97 of the matrix's bytes and the device
-// has the image's size plus kImageMargin free.  Failure is silent: the 2-bit pass runs.
+// has the image's size -- the tiles, and the lists by the plan's count of dosage-2 entries (plan_list_bytes) -- plus kImageMargin
+// free.  Failure is silent: the 2-bit pass runs.
 constexpr size_t kImageMinMatrix = 4ull << 30;
 constexpr size_t kImageMargin = 8ull << 30;
 void score_image_auto(const mih_mat *h)
@@ -357,7 +438,7 @@ void score_image_auto(const mih_mat *h)
     size_t free_b = 0, total_b = 0;
     const bool ok = plan_image(h, kDefaultHomFraction, pl) == MIH_OK && pl.p1 > 0 && (double)pl.tile_bytes <= 0.97 * (double)x_bytes &&
                     hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-                    free_b >= pl.tile_bytes + (size_t)(0.02 * (double)x_bytes) + kImageMargin &&      // (2 % of the matrix: room for the lists)
+                    free_b >= pl.tile_bytes + plan_list_bytes(h, pl) + kImageMargin &&
                     build_image(h, kDefaultHomFraction, pl, im) == MIH_OK;
     (void)hipGetLastError();
     if (ok) set_image(h, im);
