@@ -4,7 +4,7 @@
  * tools/ and the "this switch changes nothing" tests use them to sweep launch shapes, to cross-check the product's
  * kernels bit for bit against the round-1 kernel families, to run timing probes, and to drive sequences of calls on ONE
  * workspace (mih_probe_xtv_sequence: fused X'r passes; mih_probe_xv_sequence: the cached and multi-trait X beta paths of a
- * fit).  The measurement build also reads
+ * fit), and to run the GLM refit of debias! on its own (mih_probe_debias_glm).  The measurement build also reads
  * the MENDELIHT_* A/B environment switches (XTV_MAX_OPS, XTV_SLICES, XTV_NO_HALF, CV_LANES, CV_NO_MERGE,
  * CV_NO_INIT_SHARE, CV_NO_COOP, COOP_SPIN_US, CV_TRACE, INGEST_TRACE, INGEST_THREADS, TRACE_ETA, NO_SPIN, NO_ARENA, NO_RESERVE,
  * NO_RESIDENT, TOPK_RADIX8, XV_MULTI, RES_FORCE_ABORT_ES, DEBIAS_TRACE = the IRLS iterates of debias!'s GLM refit on stderr); the
@@ -43,6 +43,16 @@ int mih_probe_xtv_sequence(const mih_mat *h, const double *R, int mcap, const in
  * is not synchronised between the calls. */
 int mih_probe_xv_sequence(const mih_mat *h, int64_t max_nnz, int64_t cache_nnz, int ncalls, const int64_t *nnz, const int *m,
                           const int *flags, const int64_t *idx_cat, const double *val_cat, double *OUT, double *GATHERED);
+/* The GLM refit of debias! (csrc/debias.hip: debias_glm_device) on its own, unsharded, on the matrix's stream: y (n doubles on the
+ * host) is refitted on the k columns idx[0 .. k) (1 <= k <= p, each in [0, p)) with distribution dist, link `link` and the NegBin r
+ * nb_r; BETA receives the k coefficients in the order of idx.  GRAM0, W0, T0 (each may be null) receive what the FIRST solve
+ * consumed: the (k+1) x (k+1) reduced Gram, column-major, upper triangle valid, X'W t in its last column and t'W t in its corner;
+ * the n working weights and the n working responses eta + wrkresid at mustart(y).  They are filled as soon as that Gram is on the
+ * host, so they are valid when the call fails in the Cholesky solve or later.  IRLS_ITERS (may be null): the iterations after the
+ * first solve.  The refit's own errors (ProbitLink, X'WX not positive definite, step halving, no convergence) come back as they do
+ * from a fit. */
+int mih_probe_debias_glm(const mih_mat *h, const int64_t *idx, int64_t k, const double *y, int dist, int link, double nb_r,
+                         double *beta, double *gram0, double *w0, double *t0, int32_t *irls_iters);
 #ifdef __cplusplus
 }
 #endif

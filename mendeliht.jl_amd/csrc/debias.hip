@@ -162,6 +162,14 @@ static bool chol_solve_upper(std::vector<double> &G, int m, int k, std::vector<d
     return true;
 }
 
+#ifdef MIH_PROBES
+// mih_probe_debias_glm (below): what the FIRST delbeta() of the next refit on this thread consumed -- the reduced Gram as it came
+// off the device (the Cholesky factor overwrites the host copy) and the panel-side weights and target it was formed from.
+// Compiled into the measurement build only: the product's refit has no such branch.
+struct DebiasCapture { double *gram0, *w0, *t0; bool taken; int iters; };
+static thread_local DebiasCapture *g_db_capture = nullptr;
+#endif
+
 int debias_glm_device(const mih_mat *h, const int64_t *idx_host, int64_t k64, const double *y_dev, int dist, int link,
                       double nb_r, double *beta_out, hipStream_t s, const DebiasShard *shard)
 {
@@ -212,6 +220,15 @@ int debias_glm_device(const mih_mat *h, const int64_t *idx_host, int64_t k64, co
         hipLaunchKernelGGL(k_db_gram_reduce, dim3((unsigned)npairs), dim3(256), 0, s, part.p, tl.p, m, G.p);
         MIH_HIP(hipMemcpyAsync(Gh.data(), G.p, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost, s));
         MIH_HIP(hipStreamSynchronize(s));
+#ifdef MIH_PROBES
+        if (g_db_capture && !g_db_capture->taken) {
+            DebiasCapture &c = *g_db_capture;
+            c.taken = true;
+            if (c.gram0) std::copy(Gh.begin(), Gh.end(), c.gram0);
+            if (c.w0) MIH_HIP(hipMemcpy(c.w0, wwt.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+            if (c.t0) MIH_HIP(hipMemcpy(c.t0, target, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        }
+#endif
         for (int a = 0; a < k; ++a) del[a] = Gh[a + (size_t)m * k];
         if (!chol_solve_upper(Gh, m, k, del)) { set_error("debias: X'WX of the support columns is not positive definite"); return MIH_BAD_ARG; }
         return MIH_OK;
@@ -245,6 +262,9 @@ int debias_glm_device(const mih_mat *h, const int64_t *idx_host, int64_t k64, co
             MIH_TRY(update(0, &dev));
         }
         beta0 = trial;
+#ifdef MIH_PROBES
+        if (g_db_capture) g_db_capture->iters = it;
+#endif
         if (trace) fprintf(stderr, "debias: it %d f %g dev %.15g devold-dev %.3e\n", it, f, dev, devold - dev);
         if (devold - dev < std::fmax(1e-6 * devold, 1e-6)) { cvg = true; break; }
         if (!std::isfinite(dev)) { set_error("debias: non-finite deviance"); return MIH_BAD_ARG; }
@@ -256,3 +276,27 @@ int debias_glm_device(const mih_mat *h, const int64_t *idx_host, int64_t k64, co
 }
 
 }  // namespace mih
+
+#ifdef MIH_PROBES
+// include/mendeliht_hip_probes.h: the refit on its own, unsharded, on the matrix's stream, with what its first solve consumed.
+extern "C" int mih_probe_debias_glm(const mih_mat *h, const int64_t *idx, int64_t k, const double *y, int dist, int link, double nb_r,
+                                    double *beta, double *gram0, double *w0, double *t0, int32_t *irls_iters)
+{
+    using namespace mih;
+    if (!h || !idx || !y || !beta || k < 1 || k > h->p) { set_error("null/invalid argument"); return MIH_BAD_ARG; }
+    if (dist < MIH_NORMAL || dist > MIH_INVGAUSS || link < MIH_IDENTITY || link > MIH_SQRT) { set_error("dist = %d, link = %d", dist, link); return MIH_BAD_ARG; }
+    for (int64_t t = 0; t < k; ++t)
+        if (idx[t] < 0 || idx[t] >= h->p) { set_error("column index %lld out of range", (long long)idx[t]); return MIH_BAD_DIM; }
+    MIH_HIP(hipSetDevice(h->device));
+    DevBuf<double> dy;
+    MIH_TRY(dy.alloc((size_t)h->n));
+    MIH_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+    DebiasCapture cap{gram0, w0, t0, false, 0};
+    g_db_capture = &cap;
+    const int rc = debias_glm_device(h, idx, k, dy.p, dist, link, nb_r, beta, h->stream);
+    g_db_capture = nullptr;
+    (void)hipStreamSynchronize(h->stream);
+    if (irls_iters) *irls_iters = cap.iters;
+    return rc;
+}
+#endif

@@ -1205,3 +1205,326 @@ def model_size_cases(q=3):
     out.append(("last resident model", C["big_list"] - 64 - q, None, "scratch"))
     out.append(("first model beyond the scratch lists", C["big_list"] - 64 - q + 1, None, "host"))
     return out
+
+
+# ---- the GLM refit of debias! on its own (csrc/debias.hip through mih_probe_debias_glm): problems, the panel rebuilt on the host,
+# ---- the exact Gram with its counted bound, the closed forms in numpy and in mpmath ----
+DEBIAS_DIST = {"normal": 0, "bernoulli": 1, "poisson": 2, "negbin": 3, "gamma": 4, "invgauss": 5}
+DEBIAS_LINK = {"identity": 0, "logit": 1, "log": 2, "probit": 3, "cloglog": 4, "cauchit": 5, "inverse": 6, "invsquare": 7, "sqrt": 8}
+DEBIAS_FORMS = (("normal", "identity", 1.0), ("normal", "log", 1.0), ("bernoulli", "logit", 1.0), ("bernoulli", "cloglog", 1.0),
+                ("bernoulli", "cauchit", 1.0), ("poisson", "log", 1.0), ("poisson", "sqrt", 1.0), ("negbin", "log", 4.0), ("negbin", "log", 0.5),
+                ("gamma", "log", 1.0), ("gamma", "inverse", 1.0), ("invgauss", "log", 1.0), ("invgauss", "invsquare", 1.0))
+DEBIAS_SHAPES = ((257, 17), (1000, 48), (4097, 33))
+DEBIAS_KS = (1, 15, 16, 17, 31, 32, 33, 48)
+DEBIAS_NS = (17, 63, 64, 65, 1000, 4095, 4096, 4097, 4161)
+DEBIAS_FLAGS = ((1, 1, 1), (0, 0, 1), (0, 1, 0), (1, 0, 0))
+DEBIAS_P = 83                                   # columns of the 2-bit matrices: two full 32-column groups and a ragged one of 19
+_STORED = np.array([0, 0, 1, 2], dtype=np.int64)          # PLINK code -> stored dosage (a missing entry is stored as 0)
+
+
+def debias_gamma(n):
+    """The relative error allowed to an entry of the Gram of k_db_gram / k_db_gram_reduce, in units of sum_i |P_ia w_i P_ib|, COUNTED
+    from the kernels: a row slice holds per = ceil(n / 64) rows, each one fma step of the chain (the padding rows of a chunk add
+    +0.0 exactly); 64 additions join the slices; the product P_ia w_i is rounded once, and one more for the second-order terms."""
+    from fractions import Fraction
+    return Fraction(-(-n // 64) + 64 + 2, 2 ** 53)
+
+
+def debias_support(p, k, rng, ordered=True):
+    """k columns of 0 .. p-1 that hold column 0, column p - 1 (in the ragged last 32-column group), a run of adjacent columns across
+    the 32-column boundary (30 .. 33) and random others; ascending, or (ordered=False) in a random order."""
+    must = [0, p - 1, 31, 32, 30, 33][:k] if k > 1 else [int(rng.integers(2)) * (p - 1)]
+    rest = [int(j) for j in rng.permutation(p) if j not in must]
+    idx = np.array(must + rest[:k - len(must)], dtype=np.int64)
+    return np.sort(idx) if ordered else idx[rng.permutation(k)]
+
+
+def debias_codes(rng, n, p, miss=0.02):
+    """PLINK codes (p x n) with allele frequencies 0.15 .. 0.5 and a share `miss` of missing entries."""
+    maf = rng.uniform(0.15, 0.5, p)
+    code = np.array([0, 2, 3], dtype=np.uint8)[rng.binomial(2, maf[:, None], size=(p, n))]
+    if miss > 0:
+        code[rng.random((p, n)) < miss] = 1
+    return code
+
+
+def debias_panel_snp(code, idx, mu, sinv, center, scale, impute):
+    """The n x k panel k_db_cols_snp + k_db_cols_missing decode from the 2-bit matrix, rebuilt from the PLINK codes (p x n) and the
+    handle's own mu and sinv: ((double)g - cm) * s for a stored entry, ((impute ? mu : 0) - cm) * s for a missing one, cm = center ?
+    mu : 0, s = scale ? sinv : 1 -- one subtraction and one multiplication, each rounded once on both sides."""
+    c = np.asarray(code)[np.asarray(idx)]
+    s = np.asarray(sinv, dtype=np.float64)[idx] if scale else np.ones(len(idx))
+    cm = np.asarray(mu, dtype=np.float64)[idx] if center else np.zeros(len(idx))
+    fill = ((np.asarray(mu, dtype=np.float64)[idx] if impute else np.zeros(len(idx))) - cm) * s
+    P = (_STORED[c].astype(np.float64) - cm[:, None]) * s[:, None]
+    return np.ascontiguousarray(np.where(c == 1, fill[:, None], P).T)
+
+
+def debias_panel_dosage(num, den, idx):
+    """dosage_x of csrc/common.h on the columns idx: ((double)num - mun_j) * sc_j, 0.0 for a missing entry (dosage_host_stats)."""
+    mun, sc, _, _ = dosage_host_stats(num, den)
+    sub = num[:, idx]
+    return np.where(sub == 0xFFFF, 0.0, (sub.astype(np.float64) - mun[idx][None, :]) * sc[idx][None, :])
+
+
+def _col_ints(A):
+    """The doubles A (n x m) as Python integers over one power of two per column: A[i, c] = I[i, c] * 2 ** e[c], exactly."""
+    A = np.asarray(A, dtype=np.float64)
+    assert np.isfinite(A).all()
+    mant, ex = np.frexp(A)
+    M = np.ldexp(mant, 53).astype(np.int64)
+    ex = ex.astype(np.int64) - 53
+    nz = A != 0.0
+    e = np.where(nz, ex, np.iinfo(np.int64).max).min(axis=0)
+    e = np.where(nz.any(axis=0), e, 0)
+    shift = np.where(nz, ex - e[None, :], 0)
+    return M.astype(object) << shift.astype(object), [int(v) for v in e]
+
+
+def _abs_limbs(I, bits=18):
+    """|I| (an object array of Python integers) as float64 arrays of `bits`-bit limbs, least significant first, and the signs."""
+    sign = np.where(I < 0, -1.0, 1.0)
+    W = np.abs(I)
+    top = max(int(v).bit_length() for v in W.ravel())
+    mask = (1 << bits) - 1
+    return [((W >> (bits * l)) & mask).astype(np.float64) for l in range(max(1, -(-top // bits)))], sign
+
+
+def debias_gram_exact(P, w, bits=18):
+    """sum_i P_ia w_i P_ib and sum_i |P_ia w_i P_ib| for every (a, b), exactly, as Fractions (two m x m object arrays).  Every
+    double is an integer over a power of two; the integers are cut into 18-bit limbs and the limb matrices multiplied in float64,
+    where every product (< 2^36) and every sum over n < 2^16 rows is exact; the limbs are joined in Python integers."""
+    from fractions import Fraction
+    P = np.asarray(P, dtype=np.float64)
+    n, m = P.shape
+    assert n < 2 ** 16
+    I, e = _col_ints(P)
+    Wi, ew = _col_ints(np.asarray(w, dtype=np.float64).reshape(n, 1))
+    Q = I * Wi
+    la, sa = _abs_limbs(I, bits)
+    lq, sq = _abs_limbs(Q, bits)
+    N = np.zeros((m, m), dtype=object); S = np.zeros((m, m), dtype=object)
+    for x, ax in enumerate(la):
+        for y, qy in enumerate(lq):
+            sh = bits * (x + y)
+            N = N + ((ax * sa).T @ (qy * sq)).astype(np.int64).astype(object) * (1 << sh)
+            S = S + (ax.T @ qy).astype(np.int64).astype(object) * (1 << sh)
+    two = Fraction(2)
+    scale = np.array([[two ** (e[a] + e[b] + ew[0]) for b in range(m)] for a in range(m)], dtype=object)
+    return N * scale, S * scale
+
+
+def debias_gram_misses(G, P, w, n, exact=None):
+    """Entries of the upper triangle of G (m x m doubles, column-major in a flat array or G[a, b]) farther from the exact Gram of
+    the panel P (n x m) under the weights w than debias_gamma(n) * sum_i |P_ia w_i P_ib|.  Returns (misses, worst): misses =
+    [(a, b, got, exact as float, bound as float)], worst = the largest error in units of its bound."""
+    from fractions import Fraction
+    m = P.shape[1]
+    G = np.asarray(G, dtype=np.float64).reshape(m, m, order="F")
+    E, S = exact if exact is not None else debias_gram_exact(P, w)
+    gam = debias_gamma(n)
+    bad, worst = [], 0.0
+    for a in range(m):
+        for b in range(a, m):
+            if not np.isfinite(G[a, b]):
+                bad.append((a, b, float(G[a, b]), float(E[a, b]), float(gam * S[a, b]))); worst = np.inf
+                continue
+            err, bound = abs(Fraction(float(G[a, b])) - E[a, b]), gam * S[a, b]
+            if err > bound:
+                bad.append((a, b, float(G[a, b]), float(E[a, b]), float(bound)))
+            if err:
+                worst = max(worst, float(err / bound) if bound else np.inf)
+    return bad, worst
+
+
+def debias_gram_restated(P, w):
+    """The summation order of k_db_gram / k_db_gram_reduce in plain float64 (a multiply and an add where the kernel has one fma):
+    64 row slices of per = ceil(n / 64) rows, each a chain over its rows, joined in slice order.  m x m (the kernel forms the upper
+    tiles only)."""
+    n, m = P.shape
+    per = -(-n // 64)
+    Pw = P * np.asarray(w, dtype=np.float64)[:, None]
+    G = np.zeros((m, m))
+    for s in range(64):
+        acc = np.zeros((m, m))
+        for i in range(s * per, min((s + 1) * per, n)):
+            acc = acc + np.multiply.outer(Pw[i], P[i])
+        G = G + acc
+    return G
+
+
+def debias_forms_f64(dist, link, nb_r, y):
+    """(w0, t0): the working weight and the working response eta + wrkresid of GLM.jl at eta0 = linkfun(mustart(y)), by the closed
+    forms of csrc/fit_common.h (d_mustart, d_linkfun, d_linkinv, d_mueta, d_glmvar) in numpy float64, every intermediate rounded as
+    there."""
+    y = np.asarray(y, dtype=np.float64)
+    pi = 3.141592653589793
+    with np.errstate(all="ignore"):
+        mu0 = {"bernoulli": (y + 0.5) / 2.0, "poisson": y + 0.1, "negbin": y + np.where(y == 0.0, 1.0 / 6.0, 0.0),
+               "gamma": np.where(y == 0.0, 0.1, y)}.get(dist, y)
+        eta = {"logit": lambda m: np.log(m / (1.0 - m)), "log": np.log, "cloglog": lambda m: np.log(-np.log1p(-m)),
+               "cauchit": lambda m: np.tan(pi * (m - 0.5)), "inverse": lambda m: 1.0 / m, "invsquare": lambda m: 1.0 / (m * m),
+               "sqrt": np.sqrt, "identity": lambda m: m}[link](mu0)
+        if link == "logit":
+            e = np.exp(-np.abs(eta)); f = 1.0 + e
+            mu, me = 1.0 / (1.0 + np.exp(-eta)), e / (f * f)
+        elif link == "log":
+            mu, me = np.exp(eta), np.exp(eta)
+        elif link == "cloglog":
+            mu, me = -np.expm1(-np.exp(eta)), np.exp(eta) * np.exp(-np.exp(eta))
+        elif link == "cauchit":
+            mu, me = 0.5 + np.arctan(eta) / pi, 1.0 / (pi * (1.0 + eta * eta))
+        elif link == "inverse":
+            mu, me = 1.0 / eta, -1.0 / (eta * eta)
+        elif link == "invsquare":
+            mu = 1.0 / np.sqrt(eta); me = -mu * mu * mu / 2.0
+        elif link == "sqrt":
+            mu, me = eta * eta, 2.0 * eta
+        else:
+            mu, me = eta, np.ones_like(eta)
+        var = {"bernoulli": mu * (1.0 - mu), "poisson": mu, "negbin": mu * (1.0 + mu / nb_r), "gamma": mu * mu,
+               "invgauss": mu * mu * mu}.get(dist, np.ones_like(mu))
+        return me * me / var, eta + (y - mu) / me
+
+
+def _mp_forms():
+    """GLM.jl's closed forms in mpmath: mustart(dist, y), linkfun / linkinv / mueta(link, .), glmvar(dist, mu, r)."""
+    import mpmath as mp
+    half = mp.mpf(1) / 2
+    mustart = {"bernoulli": lambda y: (y + half) / 2, "poisson": lambda y: y + mp.mpf(1) / 10,
+               "negbin": lambda y: y + (mp.mpf(1) / 6 if y == 0 else 0), "gamma": lambda y: mp.mpf(1) / 10 if y == 0 else y}
+    linkfun = {"identity": lambda m: m, "logit": lambda m: mp.log(m / (1 - m)), "log": mp.log, "cloglog": lambda m: mp.log(-mp.log(1 - m)),
+               "cauchit": lambda m: mp.tan(mp.pi * (m - half)), "inverse": lambda m: 1 / m, "invsquare": lambda m: 1 / (m * m), "sqrt": mp.sqrt}
+    linkinv = {"identity": lambda e: e, "logit": lambda e: 1 / (1 + mp.exp(-e)), "log": mp.exp, "cloglog": lambda e: 1 - mp.exp(-mp.exp(e)),
+               "cauchit": lambda e: half + mp.atan(e) / mp.pi, "inverse": lambda e: 1 / e, "invsquare": lambda e: 1 / mp.sqrt(e),
+               "sqrt": lambda e: e * e, "probit": lambda e: mp.ncdf(e)}
+    mueta = {"identity": lambda e: mp.mpf(1), "logit": lambda e: mp.exp(-e) / (1 + mp.exp(-e)) ** 2, "log": mp.exp,
+             "cloglog": lambda e: mp.exp(e) * mp.exp(-mp.exp(e)), "cauchit": lambda e: 1 / (mp.pi * (1 + e * e)),
+             "inverse": lambda e: -1 / (e * e), "invsquare": lambda e: -1 / (2 * e * mp.sqrt(e)), "sqrt": lambda e: 2 * e,
+             "probit": lambda e: mp.npdf(e)}
+    glmvar = {"normal": lambda m, r: mp.mpf(1), "bernoulli": lambda m, r: m * (1 - m), "poisson": lambda m, r: m,
+              "negbin": lambda m, r: m * (1 + m / r), "gamma": lambda m, r: m * m, "invgauss": lambda m, r: m * m * m}
+    return mustart, linkfun, linkinv, mueta, glmvar
+
+
+def debias_forms_mp(dist, link, nb_r, y, dps=50):
+    """(w0, t0) of debias_forms_f64 as lists of mpmath numbers at `dps` digits: GLM.jl's formulas evaluated literally --
+    mu0 = mustart(y), eta0 = linkfun(mu0), mu = linkinv(eta0), w = mueta(eta0)^2 / var(mu), t = eta0 + (y - mu) / mueta(eta0)."""
+    import mpmath as mp
+    mustart, linkfun, linkinv, mueta, glmvar = _mp_forms()
+    W, T = [], []
+    with mp.workdps(dps):
+        r = mp.mpf(float(nb_r))
+        for v in np.asarray(y, dtype=np.float64):
+            yy = mp.mpf(float(v))
+            eta = linkfun[link](mustart.get(dist, lambda t: t)(yy))
+            mu, me = linkinv[link](eta), mueta[link](eta)
+            W.append(me * me / glmvar[dist](mu, r)); T.append(eta + (yy - mu) / me)
+    return W, T
+
+
+def debias_form_errors(got, exact):
+    """Per entry of got (doubles) against exact (mpmath numbers): (relative error, error in ulps of the exact value, the ulp) as
+    float arrays; an exact zero has relative error 0 when got is 0 and inf otherwise."""
+    import mpmath as mp
+    rel_, ulps, ulp = np.zeros(len(exact)), np.zeros(len(exact)), np.zeros(len(exact))
+    with mp.workdps(50):
+        for i, (g, x) in enumerate(zip(np.asarray(got, dtype=np.float64), exact)):
+            ulp[i] = float(np.spacing(abs(float(x))))
+            if not np.isfinite(g):
+                rel_[i] = ulps[i] = np.inf
+                continue
+            d = abs(mp.mpf(float(g)) - x)
+            rel_[i] = float(d / abs(x)) if x != 0 else (0.0 if d == 0 else np.inf)
+            ulps[i] = float(d / mp.mpf(ulp[i]))
+    return rel_, ulps, ulp
+
+
+def debias_refit_problem(dist, link, nb_r, n, k, attempt=0):
+    """One refit of tests/test_gpu_debias_refit.py (d): PLINK codes (DEBIAS_P x n, 2 % missing), the flags (center, scale, impute),
+    the ascending support of k columns and y.  Links that need eta in their domain without an intercept (log, inverse,
+    inverse-square, sqrt) get an uncentred matrix and positive planted coefficients with a mean linear predictor near 1.2; the
+    others a centred, scaled matrix and Gaussian coefficients with sd(eta) = 1.  Deterministic in its arguments; `attempt` is the
+    re-draw counter of DEBIAS_REDRAWS."""
+    f = DEBIAS_FORMS.index((dist, link, nb_r))
+    rng = np.random.default_rng([20280, f, n, k, attempt])
+    code = debias_codes(rng, n, DEBIAS_P)
+    idx = debias_support(DEBIAS_P, k, rng)
+    positive = link in ("log", "inverse", "invsquare", "sqrt")
+    csi = ((0, 0, 1), (0, 1, 0))[(f + k) % 2] if positive else (1, 1, 1)
+    mu, sinv = snp_host_stats(_pack(code), n)
+    X = debias_panel_snp(code, idx, mu, sinv, *csi)
+    if positive:
+        eta = X @ (rng.uniform(0.02, 0.12, k) / X.mean() * (17.0 / k))
+    else:
+        eta = X @ (rng.standard_normal(k) / np.sqrt(k))
+    mean = {"identity": lambda e: e, "log": np.exp, "logit": lambda e: 1 / (1 + np.exp(-e)), "cloglog": lambda e: -np.expm1(-np.exp(e)),
+            "cauchit": lambda e: 0.5 + np.arctan(e) / np.pi, "inverse": lambda e: 1 / e, "invsquare": lambda e: 1 / np.sqrt(e),
+            "sqrt": lambda e: e * e}[link](eta)
+    if dist == "normal":
+        y = eta + rng.standard_normal(n) if link == "identity" else mean * (1.0 + 0.1 * np.clip(rng.standard_normal(n), -3, 3))
+    elif dist == "bernoulli":
+        y = (rng.random(n) < mean).astype(np.float64)
+    elif dist == "poisson":
+        y = rng.poisson(mean).astype(np.float64)
+    elif dist == "negbin":
+        y = rng.negative_binomial(nb_r, nb_r / (mean + nb_r)).astype(np.float64)
+    elif dist == "gamma":
+        y = rng.gamma(5.0, mean / 5.0)
+    else:
+        y = rng.wald(mean, 25.0)
+    return code, csi, idx, np.ascontiguousarray(y, dtype=np.float64)
+
+
+# (dist, link, nb_r, n, k) -> attempt: cases whose first draw the oracle does not fit, or not reproducibly under another row order
+# (tests/test_debias_refit_cpu.py asserts the condition for the draws listed here and for attempt 0 everywhere else)
+DEBIAS_REDRAWS = {}
+
+
+def debias_refit_cases():
+    """Every (dist, link, nb_r, n, k, attempt) of (d): DEBIAS_FORMS x DEBIAS_SHAPES."""
+    return [(d, l, r, n, k, DEBIAS_REDRAWS.get((d, l, r, n, k), 0)) for d, l, r in DEBIAS_FORMS for n, k in DEBIAS_SHAPES]
+
+
+def debias_oracle_beta(oracle, code, csi, idx, y, dist, link, nb_r, perm=None):
+    """oracle.debias_glm on the problem (rows in the order perm), the k coefficients in the order of the ascending idx."""
+    n = code.shape[1]
+    if perm is not None:
+        code, y = code[:, perm], y[perm]
+    ox = oracle.Mat.from_bed_columns(_pack(code), n, center=csi[0], scale=csi[1], impute=csi[2])
+    mask = np.zeros(code.shape[0], np.uint8); mask[idx] = 1
+    return oracle.debias_glm(ox, mask, y, dist, link, nb_r)[np.sort(idx)]
+
+
+def debias_gram_jobs():
+    """The jobs of (a): (kind, n, k, flags or None, seed) with kind "snp", "f64", "f32" or "dosage" -- every k at n = 4097, every n
+    at k = 17, the corners of the cross product, the flags dealt round; n < k (the not-positive-definite error) on a matrix of
+    whole numbers, (0, 0, 1) without a missing entry, where the oracle forms the same Gram bit for bit; a job that succeeds follows
+    each of them."""
+    pairs = [(4097, k) for k in DEBIAS_KS] + [(n, 17) for n in DEBIAS_NS if n != 4097]
+    pairs += [(17, 1), (17, 15), (17, 16), (63, 15), (64, 16), (64, 1), (65, 32), (1000, 31), (1000, 48), (4095, 1), (4095, 33), (4096, 16), (4096, 48),
+              (4161, 33), (4161, 48), (4161, 1)]
+    jobs = [("snp", n, k, DEBIAS_FLAGS[t % 4], t) for t, (n, k) in enumerate(pairs)]
+    jobs += [("snp", 17, 33, (0, 0, 1), 100), ("snp", 63, 17, (1, 1, 1), 102), ("snp", 17, 48, (0, 0, 1), 101), ("snp", 4161, 17, (1, 0, 0), 103)]
+    for t, kind in enumerate(("f64", "f32", "dosage")):
+        jobs += [(kind, 65, 17, None, 200 + t), (kind, 1000, 33, None, 210 + t), (kind, 4097, 17, None, 220 + t)]
+    return jobs
+
+
+def debias_gram_problem(kind, n, k, flags, seed):
+    """The input of one job of debias_gram_jobs: (data, idx, y) -- data the PLINK codes (DEBIAS_P x n), an n x 40 float matrix, or
+    (num, den) of an n x 40 dosage matrix with 3 % missing; idx in a random order; y Gaussian."""
+    rng = np.random.default_rng([20281, seed, n, k])
+    if kind == "snp":
+        data = debias_codes(rng, n, DEBIAS_P, miss=0.0 if n < k else 0.02)
+        p = DEBIAS_P
+    elif kind == "dosage":
+        den, p = 255, 40
+        num = (rng.binomial(2, rng.uniform(0.15, 0.5, p), (n, p)) * den + rng.integers(-25, 26, (n, p))).clip(0, 2 * den)
+        num[rng.random((n, p)) < 0.03] = 0xFFFF
+        data = (num.astype(np.uint16), den)
+    else:
+        p = 40
+        data = rng.standard_normal((n, p)) * np.exp(rng.uniform(-2, 2, p))
+        data = np.asfortranarray(data.astype(np.float32) if kind == "f32" else data)
+    return data, debias_support(p, k, rng, ordered=False), rng.standard_normal(n) * 2.0 + 0.5

@@ -218,6 +218,13 @@ def main():
     run("debias_normal", cols, n, eta + 0.4 + rng.standard_normal(n), zz, k=8, debias=True)
     run("debias_poisson", cols, n, yp, None, k=6, d=m.Poisson(), l=m.LogLink(), debias=True)
     run("debias_k1", cols, n, eta + rng.standard_normal(n), None, k=1, debias=True, max_iter=20)
+    #      ... and 20 effects planted in the first eighth of the columns, all of them rank 0's: the other ranks decode no column
+    #      (kloc == 0) and their block of the panel starts at k_off = 20; k + 1 = 21 is two 16-column tiles of the refit's Gram.
+    #      (A generator of its own: the cases below keep their draws.)
+    r20 = np.random.default_rng(4220)
+    s20 = np.sort(r20.choice(p // 8, 20, replace=False))
+    y20 = xo.xv_sparse(s20, r20.choice([-1.0, 1.0], 20) * r20.uniform(0.5, 1.0, 20)) + 0.3 + r20.standard_normal(n)
+    run("debias_k20_one_rank", cols, n, y20, None, k=20, debias=True)
 
     # 5a". (round 6) the doubly sparse projection over the shards: groups that straddle the shard boundaries (random labels) and sorted
     #      labels, a scalar k per group (J groups of k: _choose! may fire) and a vector k (the initial projection of the gradient too)

@@ -530,6 +530,49 @@ def test_debias(mih, oracle, normal_pair, normal_data, family):
     with pytest.raises(mih.MendelIHTError):
         mih.fit_iht(np.vstack([y, y]), x, None, k=4, debias=True, verbose=False)   # multivariate: disabled in the reference
 
+def _debias_wide_problem(oracle, ox, family, k):
+    """A response with k planted effects on the shipped matrix for the debias fits beyond one 16-column Gram tile."""
+    rng = np.random.default_rng([91, k])
+    eta = _sim(oracle, ox, rng, k, scale=1.0 / np.sqrt(k))
+    if family == "normal":
+        return 2.0 * eta + 0.5 + rng.standard_normal(ox.n), {}, {}, 1e-5
+    # (effects of 0.6 / sqrt(20) and 0.9 / sqrt(40) a column: the oracle's support settles within 20 steps; weaker or stronger ones
+    # at these k send it through 40 to 200 steps of a support that keeps changing)
+    return rng.poisson(np.exp((0.3 + 0.015 * k) * eta)).astype(float), dict(d="Poisson", l="LogLink"), dict(dist="poisson", link="log"), 1e-4
+
+@pytest.mark.parametrize("k", [20, 40])
+@pytest.mark.parametrize("family", ["normal", "poisson"])
+def test_debias_support_beyond_one_gram_tile(mih, oracle, normal_pair, family, k):
+    """test_debias with k + 1 > 16: the refit's Gram has several 16 x 16 tiles (k = 20: the pairs (0, 0), (0, 1), (1, 1); k = 40: six
+    pairs), the right-hand side lives in another tile than most rows.  The assertions are test_debias's."""
+    x, ox = normal_pair
+    y, kw, okw, tol = _debias_wide_problem(oracle, ox, family, k)
+    kw = {key: getattr(mih, v)() for key, v in kw.items()}
+    res = mih.fit_iht(y, x, None, k=k, debias=True, verbose=False, **kw)
+    o = oracle.fit_iht(ox, y, None, k=k, debias=True, **okw)
+    plain = oracle.fit_iht(ox, y, None, k=k, **okw)
+    assert res.iter == o["iter"] and list(res.trace["backtracks"]) == list(o["bt_trace"])
+    assert np.array_equal(np.flatnonzero(res.beta), np.flatnonzero(o["beta"]))
+    nz = np.flatnonzero(o["beta"])
+    assert nz.size == k
+    np.testing.assert_allclose(res.beta[nz], o["beta"][nz], rtol=tol)
+    np.testing.assert_allclose(res.c, o["c"], rtol=tol)
+    np.testing.assert_allclose(res.trace["logl"], o["logl_trace"], rtol=1e-8)
+    np.testing.assert_allclose(res.trace["tol"], o["tol_trace"], rtol=1e-4, atol=1e-10)
+    assert not np.array_equal(o["tol_trace"], plain["tol_trace"])          # debiasing really happened
+
+def test_debias_cv_path_across_the_gram_tile(mih, oracle, normal_pair):
+    """cv_iht with debias over the model sizes 15, 17 and 33: the lock-step fits' call of the refit (csrc/fit_lockstep.hip) with one,
+    two and three column tiles of the Gram, against the oracle at test_debias's tolerance."""
+    x, ox = normal_pair
+    y = _debias_wide_problem(oracle, ox, "normal", 33)[0]
+    folds = hash_folds(x.n, 3)
+    mse = mih.cv_iht(y, x, None, path=[15, 17, 33], q=3, folds=folds, debias=True, verbose=False)
+    omse, _ = oracle.cv_iht(ox, y, None, path=[15, 17, 33], q=3, folds=folds, debias=True)
+    np.testing.assert_allclose(mse, omse, rtol=1e-5)
+    plain, _ = oracle.cv_iht(ox, y, None, path=[15, 17, 33], q=3, folds=folds)
+    assert not np.array_equal(omse, plain)                                 # debiasing really happened
+
 def test_snplinalg_fit_equals_dense_copy(mih, oracle):
     """test/L0_reg_test.jl:340-348, 361-363: the memory-efficient SnpLinAlg path and a dense Float64 copy of
     the same standardized matrix give the same model (here both on the GPU: 2-bit MFMA path vs f64 path)."""

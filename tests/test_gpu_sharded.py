@@ -87,6 +87,9 @@ def test_sharded_fit_matches_single_process(tmp_path, world):
         tally.ok()
         if name.startswith("group_"):        # (round 6) the doubly sparse projection over the shards did something: a model of at most J groups' worth of effects
             assert 0 < len(sh["support"]) <= {"group_random_labels": 6, "group_sorted_labels": 12, "group_vector_k": 9, "group_debias": 6}[name], (name, sh["support"])
+        if name == "debias_k20_one_rank":    # what the case is about: 20 columns, every one of them rank 0's, and the refit ran
+            lo, cnt = case["block"]
+            assert len(sh["support"]) == 20 and all(lo <= j < lo + cnt for j in sh["support"]) and sh["iter"] >= 6, (name, sh["support"], sh["iter"])
         for oc in others:                                                   # every rank returns the same model
             assert oc[name]["sharded"]["support"] == sh["support"], name
             assert oc[name]["sharded"]["beta"] == sh["beta"], name
