@@ -300,6 +300,46 @@ int mih_ld_pairs(const mih_mat *h, int64_t window, double threshold, int64_t pan
                  int64_t *col_j, int64_t *col_k, double *r, int64_t *count /* pairs found, may exceed cap */);
 int mih_ld_prune(const mih_mat *h, int64_t window, int64_t step, double threshold, int64_t panel_cols, int64_t slice_rows,
                  uint8_t *keep /* p bytes */, int64_t *n_pairs /* may be NULL */);
+/* The marginal association scan: a GLM score test of every column of a matrix by itself, given the null model of the covariates
+ * -- the single-SNP analysis every paper of the reference compares IHT against -- made on the device for a 2-bit, a dosage or a
+ * dense handle.  Definitions (tests/assoc_spec.py states them in numpy): x_ij the entry of the matrix as mih_xtv multiplies it
+ * (the handle's center / scale / impute flags apply); A (n x t, column-major, 1 <= t <= 32) the score residuals, one column per
+ * trait; w (n) the working weights >= 0, NULL = all ones; Z (n x c, column-major, 1 <= c <= 64) the covariates.  The null fit
+ * itself is the caller's (GLM.jl; mendeliht's fit_null): A = (y - mu) mu'(eta) / (phi var(mu)), w = mu'(eta)^2 / (phi var(mu)).
+ *   U_js = sum_i x_ij A_is,   b_j = sum_i x_ij w_i Z_i. (c-vector),   Q_j = sum_i x_ij^2 w_i
+ *   G = Z'WZ = L L' (unpivoted Cholesky, on the host, Float64),   V_j = Q_j - |L^-1 b_j|^2
+ *   z_js = U_js / sqrt(V_j),  beta_js = U_js / V_j,  se_j = 1 / sqrt(V_j),  neglog10p_js = -log10 erfc(|z_js| / sqrt 2)
+ * in Float64; u = L^-1 b_j is formed row by row (u_k = sum_{l <= k} Linv_kl b_l, l ascending), |u|^2 with k ascending, every
+ * operation rounded by itself.  With an intercept in span(Z) and impute = 1 the statistic does not depend on center / scale.
+ * neglog10p is evaluated on the host from z and stays finite where p itself underflows (|z| = 40 gives 349.14).
+ * Degenerate columns get NaN in z, beta, se and neglog10p: a 2-bit column without an observed genotype or monomorphic among its
+ * observed ones (decided in integers, from mih_snp_counts), and any column with V_j <= 0.
+ * U and b come from the library's fused X'R pass over R = [A | w o Z] (t + c residuals, 19 a pass).  Q of a dosage or dense
+ * handle is summed per column in a fixed order.  Q of a 2-bit handle is
+ *   Q_j = x(0)^2 W0 + x(1)^2 W1 + x(2)^2 W2 + x(miss)^2 Wm,   x(g) = ((g - [center] mu_j) [scale] sinv_j), x(miss) with g = [impute] mu_j
+ * (the sum from the left), W1 / W2 the weight of the rows with dosage 1 / 2, Wm of the column's missing rows, W0 = sum w - W1 -
+ * W2 - Wm.  With w == NULL the four are the integer counts.  Otherwise the weights enter as fixed-point integers R_i = rint(w_i
+ * 2^e), e = 53 - ilogb(max w) (so R_i < 2^54; quantum q = 2^-e, at most q / 2 per row, relative to max w), and W1, W2 come from
+ * the matrix cores: the bit planes tile & 0x11111111 and tile & 0x22222222 of the stored genotypes are the FP4 numbers 0.5 [g = 1]
+ * and 1.0 [g = 2], the 27 base-4 digits u in {0, 1, 2, 3} of R_i are the FP4 numbers u / 2, and one instruction sums a digit over
+ * the rows of a class.  A row adds a multiple of 1/4, at most 1.5, so an f32 accumulator is exact up to floor(2^24 / 6) rows:
+ * a row slice holds at most 21 845 tiles of 128 rows = 2 796 160 rows.  slice_rows is rounded up to a multiple of 128 and capped
+ * there; 0 = the library's rule: that limit, fewer where a launch would have too few work items to fill the device.  Every slice
+ * stores its per-digit sums as integers; they are added per digit in 64 bits and the digits recombined once, exactly, so W0, W1,
+ * W2, Wm are the exact sums of the R_i rounded ONCE to Float64, and with them every output is bit for bit the same whatever
+ * slice_rows and on repeated calls.  The weights have their own front end and no outlier side channel (the one of the residual
+ * front end is bypassed): the quantisation error is relative to max w, which dominates Q_j.
+ * All pointers are host pointers.  z, beta, neglog10p: p x t column-major; se: p.  wsum (may be NULL): p x 3, W1, W2, Wm of
+ * column j in wsum[3 j ..] (NaN for a handle that is not 2-bit).
+ * Device memory beyond the handle: A, Z, w, R, the fused pass's workspace, the results, and for a weighted 2-bit call 8 bytes
+ * per row, 16 per row of digit planes and 8192 bytes per (column group, slice) of integer partial sums; the sum is compared
+ * with the free memory before anything is allocated, and MIH_OOM names both byte counts.  Everything is released before the call
+ * returns; the handle is only read.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: a null handle or result pointer, t or c out of range, a NaN,
+ * infinite or negative weight, a non-finite entry of A or Z, Z'WZ not positive definite, slice_rows < 0. */
+int mih_assoc_score(const mih_mat *h, const double *A /* n x t */, int32_t t, const double *w /* n, may be NULL */,
+                    const double *Z /* n x c */, int32_t c, int64_t slice_rows, double *z /* p x t */, double *beta /* p x t */,
+                    double *se /* p */, double *neglog10p /* p x t */, double *wsum /* p x 3, may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

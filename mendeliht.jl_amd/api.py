@@ -183,6 +183,7 @@ def lib():
         "mih_ld_band": [vp, i64, i64, i64, vp, vp, vp],
         "mih_ld_pairs": [vp, i64, dbl, i64, i64, i64, vp, vp, vp, C.POINTER(i64)],
         "mih_ld_prune": [vp, i64, i64, dbl, i64, i64, vp, C.POINTER(i64)],
+        "mih_assoc_score": [vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -241,7 +242,7 @@ def exported_symbols():
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_mat_score_image", "mih_device_trim",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_assoc_score", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -429,6 +430,61 @@ class _Mat:
         out = np.empty((self.p, R.shape[1]), order="F")
         _check(lib().mih_xtv_batched_fmt(self._h, _p(R), R.shape[1], dg, _p(out)))
         return out
+
+    def score_test(self, A, w=None, Z=None, slice_rows=0, wsum=False):
+        """The score test of every column given score residuals A (n or n x t), working weights w (None: ones) and covariates Z
+        (None: an intercept) -- mih_assoc_score as it is.  Returns an AssocResult; wsum=True also keeps the class-weight sums
+        W1, W2, Wm (p x 3) of a 2-bit matrix."""
+        from .assoc import AssocResult
+        A = np.asarray(A, dtype=np.float64)
+        one = A.ndim == 1
+        A = np.asfortranarray(A[:, None] if one else A)
+        if A.ndim != 2 or A.shape[0] != self.n:
+            raise DimensionMismatch(f"A has shape {A.shape}, expected {self.n} rows")
+        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
+        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
+        if Z.ndim != 2 or Z.shape[0] != self.n:
+            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (self.n,):
+                raise DimensionMismatch(f"w has shape {w.shape}, expected ({self.n},)")
+        t, c = A.shape[1], Z.shape[1]
+        z = np.empty((self.p, t), order="F"); beta = np.empty((self.p, t), order="F"); nlp = np.empty((self.p, t), order="F")
+        se = np.empty(self.p)
+        ws = np.empty((self.p, 3)) if wsum else None
+        _check(lib().mih_assoc_score(self._h, _p(A), t, _p(w), _p(Z), c, int(slice_rows), _p(z), _p(beta), _p(se), _p(nlp), _p(ws)))
+        if one:
+            z, beta, nlp = z[:, 0].copy(), beta[:, 0].copy(), nlp[:, 0].copy()
+        return AssocResult(z, beta, se, nlp, wsum=ws)
+
+    def assoc(self, y, z=None, *, d=None, l=None, slice_rows=0):
+        """The marginal association scan: the null model y ~ z (fit_null; z=None: an intercept) and the score test of every column
+        against it.  y may be n x t for Normal traits: they share the weights, and each trait's dispersion scales its own
+        statistics.  Returns an AssocResult whose `null` is the NullModel (a list of them for several traits)."""
+        from .assoc import fit_null
+        d = Normal() if d is None else _inst(d)
+        y = np.asarray(y, dtype=np.float64)
+        zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
+        if y.ndim == 2 and not isinstance(d, Normal):
+            raise ArgumentError("several traits at once are offered for Normal traits only")
+        if y.shape[0] != self.n:
+            raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
+        if isinstance(d, Normal) and (l is None or _inst(l).code == 0):
+            nulls = [fit_null(col, zc, d, l) for col in (y.T if y.ndim == 2 else [y])]
+            rt = np.sqrt(np.array([m.phi for m in nulls]))
+            A = np.stack([(col - m.mu) / r for col, m, r in zip((y.T if y.ndim == 2 else [y]), nulls, rt)], axis=1)
+            res = self.score_test(A, None, zc, slice_rows)        # unit weights; z is exact this way, beta and se take the trait's sqrt(phi)
+            res.beta = res.beta * rt[None, :]
+            res.se = res.se[:, None] * rt[None, :]
+            if y.ndim == 1:
+                res.z, res.beta, res.se, res.neglog10p = res.z[:, 0].copy(), res.beta[:, 0].copy(), res.se[:, 0].copy(), res.neglog10p[:, 0].copy()
+            res.null = nulls if y.ndim == 2 else nulls[0]
+            return res
+        null = fit_null(y, zc, d, l)
+        res = self.score_test(null.A, null.w, zc, slice_rows)
+        res.null = null
+        return res
 
     def xv_sparse(self, idx, val):
         idx = np.ascontiguousarray(idx, dtype=np.int64)
@@ -1793,6 +1849,28 @@ def iht(plinkfile, k, d, *, phenotypes=6, covariates="", summaryfile="iht.summar
     if covariancefile and mv:
         np.savetxt(covariancefile, np.asarray(result.Σ), delimiter="\t")          # writedlm(covariancefile, result.Σ)
     return result
+
+
+def gwas(plinkfile, d, *, phenotypes=6, covariates="", outfile="gwas.txt", exclude_std_idx=(), dosage=False, device=0,
+         two_bit=False, l=None, slice_rows=0):
+    """The single-SNP association scan of a file, beside iht(): the inputs are parsed as iht parses them, the null model of the
+    covariates is fitted (fit_null) and every SNP gets its score test (x.assoc).  outfile: `chr pos SNPid ref alt z beta se
+    neglog10p`, one row per SNP, tab-separated.  Returns the AssocResult."""
+    d = _inst(d)
+    x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device, two_bit)
+    if _is_multivariate(y):
+        raise ArgumentError("gwas scans one phenotype at a time")
+    if l is None:
+        l = LogLink() if isinstance(d, NegativeBinomial) else canonicallink(d)
+    res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows)
+    if outfile:
+        chrom, pos, ids, a1, a2 = info
+        with open(outfile, "w") as f:
+            f.write("chr\tpos\tSNPid\tref\talt\tz\tbeta\tse\tneglog10p\n")
+            for j in range(x.p):
+                f.write(f"{chrom[j]}\t{pos[j]}\t{ids[j]}\t{a1[j]}\t{a2[j]}\t{float(res.z[j])!r}\t{float(res.beta[j])!r}\t"
+                        f"{float(res.se[j])!r}\t{float(res.neglog10p[j])!r}\n")
+    return res
 
 
 def print_cv_results(io, errors, path, k):

@@ -1,0 +1,162 @@
+"""The host side of the marginal association scan (mih_assoc_score): the null model of the covariates, fitted in numpy, and the
+result of the scan.  The C ABI takes score residuals and working weights; a Julia caller has GLM.jl for them, this mirror has
+fit_null -- GLM.jl's IRLS (its starting values, working response and deviance stopping rule) for every family and link the fits
+accept."""
+import math
+import statistics
+
+import numpy as np
+
+_ND = statistics.NormalDist()
+_erfc = np.frompyfunc(math.erfc, 1, 1)
+_ndtri = np.frompyfunc(_ND.inv_cdf, 1, 1)
+_EPS = np.finfo(np.float64).eps
+
+
+def _f(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def _ndtr(x):
+    return 0.5 * _f(_erfc(-_f(x) / math.sqrt(2.0)))
+
+
+def _npdf(x):
+    return np.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+# link code (api.*Link.code) -> (linkfun, linkinv, mueta), GLM.jl's glmtools.jl closed forms
+LINKS = {
+    0: (lambda mu: mu, lambda eta: eta, lambda eta: np.ones_like(eta)),
+    1: (lambda mu: np.log(mu / (1.0 - mu)), lambda eta: 1.0 / (1.0 + np.exp(-eta)),
+        lambda eta: np.exp(-np.abs(eta)) / (1.0 + np.exp(-np.abs(eta))) ** 2),
+    2: (np.log, np.exp, np.exp),
+    3: (lambda mu: _f(_ndtri(np.clip(mu, 1e-300, 1.0 - 1e-16))), _ndtr, lambda eta: np.maximum(_npdf(eta), _EPS)),
+    4: (lambda mu: np.log(-np.log1p(-mu)), lambda eta: np.clip(-np.expm1(-np.exp(eta)), _EPS, 1.0 - _EPS),
+        lambda eta: np.maximum(np.exp(eta) * np.exp(-np.exp(eta)), _EPS)),
+    5: (lambda mu: np.tan(math.pi * (mu - 0.5)), lambda eta: 0.5 + np.arctan(eta) / math.pi,
+        lambda eta: 1.0 / (math.pi * (1.0 + eta * eta))),
+    6: (lambda mu: 1.0 / mu, lambda eta: 1.0 / eta, lambda eta: -1.0 / (eta * eta)),
+    7: (lambda mu: 1.0 / (mu * mu), lambda eta: 1.0 / np.sqrt(eta), lambda eta: -(1.0 / np.sqrt(eta)) ** 3 / 2.0),
+    8: (np.sqrt, lambda eta: eta * eta, lambda eta: 2.0 * eta),
+}
+
+
+def _xlogy(x, y):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(x == 0.0, 0.0, x * np.log(y))
+
+
+# family code (api distributions) -> (variance(mu, r), unit deviance summed (y, mu, r), mustart(y), dispersion estimated?)
+FAMILIES = {
+    0: (lambda mu, r: np.ones_like(mu), lambda y, mu, r: np.sum((y - mu) ** 2), lambda y: y.copy(), True),
+    1: (lambda mu, r: mu * (1.0 - mu), lambda y, mu, r: -2.0 * np.sum(_xlogy(y, mu) + _xlogy(1.0 - y, 1.0 - mu)),
+        lambda y: (y + 0.5) / 2.0, False),
+    2: (lambda mu, r: mu, lambda y, mu, r: 2.0 * np.sum(_xlogy(y, y / mu) - (y - mu)), lambda y: y + 0.1, False),
+    3: (lambda mu, r: mu + mu * mu / r,
+        lambda y, mu, r: 2.0 * np.sum(_xlogy(y, y / mu) - (y + r) * np.log((y + r) / (mu + r))),
+        lambda y: y + (y == 0.0) / 6.0, False),
+    4: (lambda mu, r: mu * mu, lambda y, mu, r: -2.0 * np.sum(np.log(y / mu) - (y - mu) / mu), lambda y: y.copy(), True),
+    5: (lambda mu, r: mu ** 3, lambda y, mu, r: np.sum((y - mu) ** 2 / (y * mu * mu)), lambda y: y.copy(), True),
+}
+_CANONICAL = {0: 0, 1: 1, 2: 2, 3: 2, 4: 6, 5: 7}
+
+
+class NullModel:
+    """The fitted null model y ~ Z: coefficients gamma, eta = Z gamma, mu, the dispersion phi, and what the score test takes --
+    A = (y - mu) mu'(eta) / (phi var(mu)) and w = mu'(eta)^2 / (phi var(mu))."""
+    def __init__(self, gamma, eta, mu, phi, A, w, dev, iters, converged):
+        self.gamma, self.eta, self.mu, self.phi, self.A, self.w = gamma, eta, mu, phi, A, w
+        self.dev, self.iters, self.converged = dev, iters, converged
+
+    def __repr__(self):
+        return f"NullModel(c={self.gamma.size}, phi={self.phi!r}, dev={self.dev!r}, iters={self.iters}, converged={self.converged})"
+
+
+def _codes(d, l):
+    d = d() if isinstance(d, type) else d
+    l = l() if isinstance(l, type) else l
+    dc = int(d.code)
+    if dc not in FAMILIES:
+        raise ValueError(f"fit_null: no univariate GLM family for {d!r}")
+    lc = _CANONICAL[dc] if l is None else int(l.code)
+    if lc not in LINKS:
+        raise ValueError(f"fit_null: unknown link {l!r}")
+    return dc, lc, float(getattr(d, "r", 1.0))
+
+
+def _wls(z, wt, resp):
+    sw = np.sqrt(wt)
+    return np.linalg.lstsq(z * sw[:, None], resp * sw, rcond=None)[0]
+
+
+def fit_null(y, z, d, l=None, tol=1e-8, max_iter=100, est_r="None"):
+    """IRLS fit of y ~ z for family d and link l (None: the canonical link, LogLink for NegativeBinomial), as GLM.jl runs it:
+    mustart by family, working response eta + (y - mu) / mu'(eta) with weights mu'(eta)^2 / var(mu), weighted least squares, step
+    halving while the deviance is not finite or rises, stop when |dev - dev_old| <= max(tol dev, tol).  The dispersion: RSS / (n - c)
+    for Normal, Pearson chi^2 / (n - c) for Gamma and InverseGaussian, 1 otherwise; NegativeBinomial takes its r as given (est_r is
+    refused: the score test conditions on a known r)."""
+    if est_r not in (None, "None", False):
+        raise ValueError("fit_null: est_r is not supported; give NegativeBinomial(r) its r")
+    y, z = _f(y), _f(z)
+    if z.ndim == 1:
+        z = z[:, None]
+    n, c = z.shape
+    if y.shape != (n,):
+        raise ValueError(f"fit_null: y has shape {y.shape}, expected ({n},)")
+    dc, lc, r = _codes(d, l)
+    variance, deviance, mustart, has_phi = FAMILIES[dc]
+    linkfun, linkinv, mueta = LINKS[lc]
+    with np.errstate(all="ignore"):
+        if dc == 0 and lc == 0:                       # one exact least-squares step
+            gamma = np.linalg.lstsq(z, y, rcond=None)[0]
+            eta = z @ gamma
+            mu, dev, iters, converged = eta, float(np.sum((y - eta) ** 2)), 1, True
+        else:
+            mu = mustart(y)
+            eta = linkfun(mu)
+            dev, gamma, converged, iters = float(deviance(y, mu, r)), np.zeros(c), False, 0
+            for iters in range(1, max_iter + 1):
+                me = mueta(eta)
+                new = _wls(z, me * me / variance(mu, r), eta + (y - mu) / me)
+                step = 1.0
+                for _ in range(30):
+                    g = gamma + step * (new - gamma) if iters > 1 else new
+                    eta_n = z @ g
+                    mu_n = linkinv(eta_n)
+                    dev_n = float(deviance(y, mu_n, r))
+                    if math.isfinite(dev_n) and (iters == 1 or dev_n <= dev + tol * abs(dev)):
+                        break
+                    if iters == 1:
+                        raise FloatingPointError("fit_null: the first IRLS step has no finite deviance")
+                    step *= 0.5
+                gamma, eta, mu = g, eta_n, mu_n
+                done = abs(dev - dev_n) <= max(tol * abs(dev_n), tol)
+                dev = dev_n
+                if done:
+                    converged = True
+                    break
+        me, var = mueta(eta), variance(mu, r)
+        phi = 1.0
+        if has_phi:
+            phi = float(np.sum((y - mu) ** 2 / var) / (n - c))
+        A = (y - mu) * me / (phi * var)
+        w = me * me / (phi * var)
+    return NullModel(gamma, eta, mu, phi, A, w, dev, iters, converged)
+
+
+class AssocResult:
+    """z, beta, neglog10p: p (one trait) or p x t; se likewise.  NaN marks a degenerate column.  null: the NullModel (a list of
+    them for several Normal traits)."""
+    def __init__(self, z, beta, se, neglog10p, null=None, wsum=None):
+        self.z, self.beta, self.se, self.neglog10p, self.null, self.wsum = z, beta, se, neglog10p, null, wsum
+
+    def top(self, k, trait=0):
+        """The k columns with the largest |z| of a trait (0-based, by falling |z|; ties by index; degenerate columns never)."""
+        a = np.abs(self.z if self.z.ndim == 1 else self.z[:, trait])
+        ok = np.flatnonzero(~np.isnan(a))
+        order = ok[np.lexsort((ok, -a[ok]))]
+        return order[:int(k)]
+
+    def __repr__(self):
+        return f"AssocResult(p={self.z.shape[0]}, traits={1 if self.z.ndim == 1 else self.z.shape[1]})"
