@@ -340,6 +340,54 @@ int mih_ld_prune(const mih_mat *h, int64_t window, int64_t step, double threshol
 int mih_assoc_score(const mih_mat *h, const double *A /* n x t */, int32_t t, const double *w /* n, may be NULL */,
                     const double *Z /* n x c */, int32_t c, int64_t slice_rows, double *z /* p x t */, double *beta /* p x t */,
                     double *se /* p */, double *neglog10p /* p x t */, double *wsum /* p x 3, may be NULL */);
+/* mih_assoc_score for ONE Bernoulli trait with the logit link, with a saddlepoint approximation (SPA) of the p-value beside the
+ * normal one: with few cases and rare alleles the score statistic is skewed and the normal tail overstates significance by
+ * orders of magnitude.  z, beta, se and neglog10p are mih_assoc_score's for t = 1, bit for bit.  tests/spa_spec.py states the
+ * following in numpy.  A = y - mu and w = mu (1 - mu) of the caller's null fit (which makes Z'A = 0), eta (n) its linear predictor
+ * h_i; mu_i = sigma(h_i).  Per column j, with U_j, b_j, V_j, z_j and Linv as above:
+ *   alpha_j = Linv' (Linv b_j) = G^-1 b_j        (u = Linv b_j as above; alpha_k = sum_{l >= k} Linv_lk u_l, l ascending)
+ *   c_i = x_ij - sum_k Z_ik alpha_jk              (k ascending from 0; the covariate-adjusted genotype)
+ *   K(t)   = sum_i [softplus(h_i + c_i t) - softplus(h_i)] - t sum_i c_i mu_i
+ *   K'(t)  = sum_i c_i [sigma(h_i + c_i t) - mu_i]
+ *   K''(t) = sum_i c_i^2 sigma(h_i + c_i t) (1 - sigma(h_i + c_i t))
+ * where, for x = h_i + c_i t, e = exp(-|x|) and r = 1 / (1 + e): sigma(x) = r (x >= 0) or e r, sigma (1 - sigma) = (e r) r,
+ * softplus(x) = max(x, 0) + log1p(e) -- nothing overflows at any t; mu_i comes from the same expressions, so K'(0) = 0 term by
+ * term.  q = U_j; the statistic ranges over [S_min, S_max] = [sum_i min(c_i, 0), sum_i max(c_i, 0)] - sum_i c_i mu_i.
+ * A tail at target s != 0: solve K'(t_hat) = s; w = sign(t_hat) sqrt(2 (t_hat s - K(t_hat))), v = t_hat sqrt(K''(t_hat)),
+ * r = w + log(v / w) / w; the tail is log Phi(-|r|) by the arithmetic of neglog10p.  The root: Newton from t = 0, safeguarded by
+ * the bracket (lo, hi) of the signs of f = K'(t) - s seen so far -- a step that leaves it (or is NaN) becomes the midpoint where
+ * both ends exist, and while the outer end is missing 2 t (1 or -1 from t = 0); it stops when |f| <= 2^-30 sqrt(V_j) and then
+ * takes one more Newton step (v is first-order sensitive to t_hat), after at most 64 evaluations of (K', K''); K and K'' at
+ * t_hat take one more pass.  A tail is ACCEPTED when the iteration converged, t_hat is finite, K''(t_hat) >= 2^-20 V_j and r is
+ * finite, not 0 and has the sign of t_hat.  (The third: where every carrier is a case the statistic sits at the end of its
+ * range, K' reaches s only as t -> infinity, the float iteration "converges" far out with K'' / V ~ 1e-11 and r means nothing.)
+ * The column: state 0 (not tried) if it is degenerate or |z_j| < cutoff, neglog10p_spa = neglog10p.  Otherwise tail 0 has
+ * target +|q| and tail 1 has -|q|; the one on the side of q is always computed, the other contributes exactly 0 and is not
+ * computed if its target is >= S_max (tail 0) or <= S_min (tail 1).  Every computed tail accepted: state 1, neglog10p_spa =
+ * -log10(exp(l_0) + exp(l_1)) formed as a log-sum-exp, finite where p underflows.  Any computed tail refused: state 2,
+ * neglog10p_spa = neglog10p (the normal value, as SAIGE falls back).  t_hat (may be NULL): p x 2 column-major, the roots of
+ * tail 0 and tail 1, NaN where a tail was not computed or did not converge.  cutoff >= 0; +inf tries no column.
+ * On the device: the columns with |z_j| >= cutoff are compacted in column order, alpha_j is formed for them, and one 256-thread
+ * workgroup owns a flagged column for the whole solve of both tails.  It reads the column through the handle's decode (2-bit,
+ * dosage, dense f64 / f32) and forms c_i ONCE into a slab of n doubles of its own (at most 2048 workgroups run, each walks
+ * several columns): an evaluation is then one 8-byte load, one exp and one division per row whatever c is, where forming c_i
+ * anew would cost c + 1 loads and c multiply-adds per row in each of the dozen evaluations of a column.  Nothing is staged
+ * in LDS by n; the one n-dependent path: a pass loads a thread's rows four at a time (its loads' latency bounds it otherwise) and
+ * the last 0 .. 3 singly -- n <= 768 has single rows only, n >= 1024 both kinds in every thread -- adding in row order either way.  Every sum is taken per thread over its rows tid, tid + 256, ... in ascending
+ * order and then over a fixed tree of the 256 partial sums, without atomics and with contraction off; the loop's control values
+ * are the same in every lane.  All sums span the whole column inside one workgroup and U, b, V are bit-reproducible, so
+ * neglog10p_spa, state and t_hat are bit for bit the same whatever slice_rows and on repeated calls.  The finish of a column
+ * (w, v, r, the tail, the log-sum-exp) is made on the host from t_hat, K(t_hat), K''(t_hat) (csrc/spa_finish.h).
+ * Device memory beyond mih_assoc_score's: 24 bytes per row (eta, mu, softplus(eta)), 8 (c + 11) bytes per column at most (the
+ * flagged indices, alpha, the tails), and min(p, 2048) slabs of 8 n bytes; it is added to the scan's and compared with the free
+ * memory before anything is allocated, MIH_OOM names both byte counts.  Everything is released before the call returns; the
+ * handle is only read.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: everything mih_assoc_score refuses (with t = 1), a null w,
+ * eta, neglog10p_spa or state, a non-finite eta, a negative or NaN cutoff. */
+int mih_assoc_score_spa(const mih_mat *h, const double *A /* n: y - mu */, const double *w /* n: mu (1 - mu) */,
+                        const double *Z /* n x c */, int32_t c, const double *eta /* n */, double cutoff, int64_t slice_rows,
+                        double *z /* p */, double *beta /* p */, double *se /* p */, double *neglog10p /* p */,
+                        double *neglog10p_spa /* p */, uint8_t *state /* p */, double *t_hat /* p x 2, may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

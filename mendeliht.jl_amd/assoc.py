@@ -147,13 +147,20 @@ def fit_null(y, z, d, l=None, tol=1e-8, max_iter=100, est_r="None"):
 
 class AssocResult:
     """z, beta, neglog10p: p (one trait) or p x t; se likewise.  NaN marks a degenerate column.  null: the NullModel (a list of
-    them for several Normal traits)."""
-    def __init__(self, z, beta, se, neglog10p, null=None, wsum=None):
+    them for several Normal traits).  With the saddlepoint pass (score_test_spa, assoc(..., spa=True)): neglog10p_spa (p),
+    spa_state (p, uint8: 0 not tried, 1 saddlepoint value, 2 refused -- the normal value) and t_hat (p x 2: the roots of the
+    upper and the lower tail, NaN where none); None without it."""
+    def __init__(self, z, beta, se, neglog10p, null=None, wsum=None, neglog10p_spa=None, spa_state=None, t_hat=None):
         self.z, self.beta, self.se, self.neglog10p, self.null, self.wsum = z, beta, se, neglog10p, null, wsum
+        self.neglog10p_spa, self.spa_state, self.t_hat = neglog10p_spa, spa_state, t_hat
 
     def top(self, k, trait=0):
-        """The k columns with the largest |z| of a trait (0-based, by falling |z|; ties by index; degenerate columns never)."""
-        a = np.abs(self.z if self.z.ndim == 1 else self.z[:, trait])
+        """The k columns with the largest |z| of a trait (0-based, by falling |z|; ties by index; degenerate columns never); with
+        the saddlepoint pass, the k columns with the largest neglog10p_spa."""
+        if self.neglog10p_spa is not None:
+            a = np.asarray(self.neglog10p_spa)
+        else:
+            a = np.abs(self.z if self.z.ndim == 1 else self.z[:, trait])
         ok = np.flatnonzero(~np.isnan(a))
         order = ok[np.lexsort((ok, -a[ok]))]
         return order[:int(k)]

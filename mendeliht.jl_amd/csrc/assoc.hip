@@ -10,6 +10,7 @@
 // class.  Everything up to one rounding per class sum is an integer: no result depends on how the rows are cut into slices.
 #include "grm.h"
 #include "normal_tail.h"
+#include "assoc_spa.h"
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -324,17 +325,19 @@ static bool assoc_null_factor(const double *Z, const double *w, int64_t n, int c
 
 static unsigned blocks_of(int64_t items) { return (unsigned)((items + 255) / 256); }
 
-}  // namespace mih
+// what mih_assoc_score_spa adds to a call (nullptr: the plain scan)
+struct SpaCall { const double *eta; double cutoff; double *neglog10p_spa; uint8_t *state; double *t_hat; };
 
-using namespace mih;
-
-extern "C" {
-
-int mih_assoc_score(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
-                    double *z, double *beta, double *se, double *neglog10p, double *wsum)
+// the body of both entry points
+static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
+                           double *z, double *beta, double *se, double *neglog10p, double *wsum, const SpaCall *spa)
 {
     // ---- refusals: nothing allocated, nothing written ----
     if (!h || !A || !Z || !z || !beta || !se || !neglog10p) { set_error("mih_assoc_score: null argument"); return MIH_BAD_ARG; }
+    if (spa) {
+        if (!w || !spa->eta || !spa->neglog10p_spa || !spa->state) { set_error("mih_assoc_score_spa: null argument"); return MIH_BAD_ARG; }
+        if (!(spa->cutoff >= 0.0)) { set_error("mih_assoc_score_spa: cutoff must not be negative or NaN, got %g", spa->cutoff); return MIH_BAD_ARG; }
+    }
     if (t < 1 || t > 32) { set_error("mih_assoc_score: 1 <= t <= 32 traits, got %d", (int)t); return MIH_BAD_ARG; }
     if (c < 1 || c > 64) { set_error("mih_assoc_score: 1 <= c <= 64 covariates, got %d", (int)c); return MIH_BAD_ARG; }
     if (slice_rows < 0) { set_error("mih_assoc_score: slice_rows must not be negative, got %lld", (long long)slice_rows); return MIH_BAD_ARG; }
@@ -348,6 +351,7 @@ int mih_assoc_score(const mih_mat *h, const double *A, int32_t t, const double *
         }
     if (!all_finite(A, (size_t)n * (size_t)t)) { set_error("mih_assoc_score: a score residual is not finite"); return MIH_BAD_ARG; }
     if (!all_finite(Z, (size_t)n * (size_t)c)) { set_error("mih_assoc_score: a covariate is not finite"); return MIH_BAD_ARG; }
+    if (spa && !all_finite(spa->eta, (size_t)n)) { set_error("mih_assoc_score_spa: a linear predictor is not finite"); return MIH_BAD_ARG; }
     std::vector<double> Linv;
     if (!assoc_null_factor(Z, w, n, c, Linv)) { set_error("mih_assoc_score: Z'WZ is not positive definite"); return MIH_BAD_ARG; }
 
@@ -381,8 +385,15 @@ int mih_assoc_score(const mih_mat *h, const double *A, int32_t t, const double *
         need += ops * (double)nblk * 64.0 * 24.0 + 16.0 * m * (double)ncg * 32.0 * 8.0 + 32.0 * dp;      // the fused pass's digit planes and partial sums; Wc
         if (classes) need += 8.0 * (double)h->n_pad + (double)nblk * 1024.0 + (double)nsl * (double)ncg * 8192.0 + 16.0 * dp;   // R_i, their digit planes, the integer partials, Tm
     }
+    const double need_spa = spa ? assoc_spa_bytes(n, p, (int)c) : 0.0;
+    need += need_spa;
     size_t free_b = 0, total_b = 0;
     MIH_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (spa && need > (double)free_b) {
+        set_error("mih_assoc_score_spa: the scan needs %.0f bytes of device memory and the saddlepoint pass %.0f more (the linear predictor, the flagged columns' alpha and tails, %lld slabs of %lld adjusted genotypes), %.0f bytes are free",
+                  need - need_spa, need_spa, (long long)std::min<int64_t>(p, kSpaSlabs), (long long)n, (double)free_b);
+        return MIH_OOM;
+    }
     if (need > (double)free_b) {
         set_error("mih_assoc_score: %d traits and %d covariates on %lld x %lld (residuals, the fused pass, class sums and results) need %.0f bytes of device memory, %.0f bytes are free",
                   (int)t, (int)c, (long long)n, (long long)p, need, (double)free_b);
@@ -488,14 +499,43 @@ int mih_assoc_score(const mih_mat *h, const double *A, int32_t t, const double *
         MIH_HIP(hipMemcpyAsync(hw.data(), Wc.p, sizeof(double) * (size_t)(4 * p), hipMemcpyDeviceToHost, s));
     }
     MIH_HIP(hipStreamSynchronize(s));
+    std::vector<double> hn(hz.size()), spa_v, spa_t;
+    std::vector<uint8_t> spa_s;
+    for (size_t i = 0; i < hz.size(); ++i) hn[i] = neglog10p_of_z(hz[i]);
+    if (spa) MIH_TRY(assoc_spa_run(h, s, (int)c, S.p, V.p, zd.p, Ld.p, Zd.p, spa->eta, spa->cutoff, hn.data(), spa_v, spa_s, spa_t));
     memcpy(z, hz.data(), sizeof(double) * hz.size());
     memcpy(beta, hb.data(), sizeof(double) * hb.size());
     memcpy(se, hs.data(), sizeof(double) * hs.size());
-    for (size_t i = 0; i < hz.size(); ++i) neglog10p[i] = neglog10p_of_z(hz[i]);
+    memcpy(neglog10p, hn.data(), sizeof(double) * hn.size());
+    if (spa) {
+        memcpy(spa->neglog10p_spa, spa_v.data(), sizeof(double) * spa_v.size());
+        memcpy(spa->state, spa_s.data(), spa_s.size());
+        if (spa->t_hat) memcpy(spa->t_hat, spa_t.data(), sizeof(double) * spa_t.size());
+    }
     if (wsum)
         for (int64_t j = 0; j < p; ++j)
             for (int k = 0; k < 3; ++k) wsum[3 * j + k] = snp ? hw[(size_t)(4 * j + 1 + k)] : std::numeric_limits<double>::quiet_NaN();
     return MIH_OK;
+}
+
+}  // namespace mih
+
+using namespace mih;
+
+extern "C" {
+
+int mih_assoc_score(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
+                    double *z, double *beta, double *se, double *neglog10p, double *wsum)
+{
+    return assoc_score_run(h, A, t, w, Z, c, slice_rows, z, beta, se, neglog10p, wsum, nullptr);
+}
+
+int mih_assoc_score_spa(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, const double *eta, double cutoff,
+                        int64_t slice_rows, double *z, double *beta, double *se, double *neglog10p, double *neglog10p_spa, uint8_t *state,
+                        double *t_hat)
+{
+    const SpaCall spa = {eta, cutoff, neglog10p_spa, state, t_hat};
+    return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, &spa);
 }
 
 }  // extern "C"
