@@ -388,6 +388,51 @@ int mih_assoc_score_spa(const mih_mat *h, const double *A /* n: y - mu */, const
                         const double *Z /* n x c */, int32_t c, const double *eta /* n */, double cutoff, int64_t slice_rows,
                         double *z /* p */, double *beta /* p */, double *se /* p */, double *neglog10p /* p */,
                         double *neglog10p_spa /* p */, uint8_t *state /* p */, double *t_hat /* p x 2, may be NULL */);
+/* mih_assoc_score for ONE Bernoulli trait with the logit link, with a Firth-penalised effect size and likelihood-ratio p-value
+ * beside the score test's: beta = U / V is a one-step estimate, far from any likelihood estimate on a skewed column, and where
+ * every carrier is a case the saddlepoint approximation is refused (state 2 above) and the maximum-likelihood estimate is
+ * infinite.  This is the approximate Firth test of REGENIE: the covariates' effects are held at the null fit as an offset, and
+ * the one-parameter logistic likelihood in the adjusted genotype, with Jeffreys' penalty, is maximised per column; the estimate
+ * is finite under complete separation.  z, beta, se and neglog10p are mih_assoc_score's for t = 1, bit for bit.
+ * tests/firth_spec.py states the following in numpy.  A, w, eta, c_i, h_i, mu_i, K, q = U_j and V_j are those of
+ * mih_assoc_score_spa.  Per row, with x = h_i + c_i beta, e = exp(-|x|), r = 1 / (1 + e):
+ *   sigma = r (x >= 0) or e r,   s = (e r) r,   d = (1 - e) r,   omega = -d (x >= 0) or d          (omega = 1 - 2 sigma)
+ *   K1 = sum c (sigma - mu)   K2 = sum (c c) s   K3 = sum ((c c) c) (s omega)   K4 = sum ((c c) (c c)) (s (1 - 6 s))
+ * the first four derivatives of K: the one-parameter model has log-likelihood beta q - K(beta), score q - K1 and information K2,
+ * so at beta = 0 it reproduces the scan's U and V.  The penalised log-likelihood relative to beta = 0 is
+ *   L*(beta) = beta q - K(beta) + log(K2(beta) / K2(0)) / 2,
+ * stationary where g(beta) = q,  g = K1 - (K3 / K2) / 2,  g' = D = K2 - ((K4 K2 - K3 K3) / (K2 K2)) / 2  (D := K2 where D is not
+ * finite or not > 0).  The root: Newton from beta = 0 with slope D under the safeguard of the saddlepoint root above (bracket,
+ * midpoint, doubling; |g - q| <= 2^-30 sqrt(V_j), then one more Newton step; at most 64 evaluations); an evaluation whose g - q is
+ * not finite ends the column as not converged.  A root always exists: g - q has opposite signs at -inf and +inf.  One more pass at
+ * beta_hat gives K(beta_hat) and K2(beta_hat); I0 is K2 of the first evaluation (beta = 0; the kernel's own sum, not V).
+ *   dev = 2 (beta_hat q - K(beta_hat) + log(K2(beta_hat) / I0) / 2)   (negative: 0)
+ *   beta_firth = beta_hat,   se_firth = 1 / sqrt(K2(beta_hat)),   neglog10p_firth = -log10 erfc(sqrt(dev / 2))   (as neglog10p of z = sqrt dev)
+ * firth_state: 0 (not tried) if the column is degenerate or |z_j| < cutoff; 1 if the iteration converged, beta_hat and dev are
+ * finite and K2(beta_hat) is finite and >= 2^-40 V_j; 2 otherwise.  In states 0 and 2 the three Firth outputs are beta, se and
+ * neglog10p bit for bit.  beta_firth is per unit of the entry x_ij, like beta.  firth_evals (may be NULL): the evaluations of
+ * (K1 .. K4) a column took, 0 where it was not tried.  cutoff >= 0; +inf tries no column.
+ * neglog10p_spa != NULL: the saddlepoint pass of mih_assoc_score_spa runs on the same selection (the same cutoff) in the same
+ * call; spa_state is then required, t_hat may be NULL, and the three are bit for bit those of mih_assoc_score_spa.
+ * neglog10p_spa == NULL: no saddlepoint pass, spa_state and t_hat are not touched.
+ * On the device: the selection, alpha and the slabs of c_i are those of mih_assoc_score_spa, held once for both passes; one
+ * 256-thread workgroup owns a flagged column for the whole solve, an evaluation is one 8-byte load beside eta_i and mu_i, one exp
+ * and one division per row and carries four sums, each taken per thread over its rows tid, tid + 256, ... in ascending order
+ * (four rows' loads ahead from n = 769 on) and then over a fixed tree, without atomics and with contraction off; the control
+ * values are the same in every lane.  All Firth outputs, firth_evals included, are bit for bit the same whatever slice_rows and
+ * on repeated calls.  The finish of a column is made on the host (csrc/firth_finish.h).
+ * Device memory beyond mih_assoc_score's: what mih_assoc_score_spa needs without its tails (with them where the saddlepoint pass
+ * runs too) and 56 bytes per column for the roots; the sum is compared with the free memory before anything is allocated,
+ * MIH_OOM names the byte counts.  Everything is released before the call returns; the handle is only read.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: everything mih_assoc_score_spa refuses (spa_state only where
+ * neglog10p_spa is given), a null beta_firth, se_firth, neglog10p_firth or firth_state. */
+int mih_assoc_score_firth(const mih_mat *h, const double *A /* n: y - mu */, const double *w /* n: mu (1 - mu) */,
+                          const double *Z /* n x c */, int32_t c, const double *eta /* n */, double cutoff, int64_t slice_rows,
+                          double *z /* p */, double *beta /* p */, double *se /* p */, double *neglog10p /* p */,
+                          double *beta_firth /* p */, double *se_firth /* p */, double *neglog10p_firth /* p */,
+                          uint8_t *firth_state /* p */, int32_t *firth_evals /* p, may be NULL; 0 where not tried */,
+                          double *neglog10p_spa /* p, may be NULL: no saddlepoint pass */, uint8_t *spa_state /* p */,
+                          double *t_hat /* p x 2, may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

@@ -185,6 +185,7 @@ def lib():
         "mih_ld_prune": [vp, i64, i64, dbl, i64, i64, vp, C.POINTER(i64)],
         "mih_assoc_score": [vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp],
         "mih_assoc_score_spa": [vp, vp, vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp],
+        "mih_assoc_score_firth": [vp, vp, vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -243,7 +244,7 @@ def exported_symbols():
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_mat_score_image", "mih_device_trim",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_assoc_score", "mih_assoc_score_spa", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_assoc_score", "mih_assoc_score_spa", "mih_assoc_score_firth", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -482,26 +483,65 @@ class _Mat:
                                          _p(z), _p(beta), _p(se), _p(nlp), _p(spa), _p(state), _p(that)))
         return AssocResult(z, beta, se, nlp, neglog10p_spa=spa, spa_state=state, t_hat=that)
 
-    def assoc(self, y, z=None, *, d=None, l=None, slice_rows=0, spa=False, spa_cutoff=2.0):
+    def score_test_firth(self, A, w, Z, eta, cutoff=2.0, slice_rows=0, spa=False):
+        """The score test of every column for one Bernoulli trait with the logit link, with the Firth-penalised effect size and
+        likelihood-ratio p-value of the columns with |z| >= cutoff beside it -- mih_assoc_score_firth as it is; the arguments are
+        those of score_test_spa.  Returns an AssocResult with beta_firth, se_firth, neglog10p_firth, firth_state (0 not tried,
+        1 penalised-likelihood values, 2 refused: the plain values) and firth_evals; spa=True runs the saddlepoint pass on the
+        same selection in the same call and fills neglog10p_spa, spa_state and t_hat as score_test_spa does."""
+        from .assoc import AssocResult
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        eta = np.ascontiguousarray(eta, dtype=np.float64)
+        for name, v in (("A", A), ("w", w), ("eta", eta)):
+            if v.shape != (self.n,):
+                raise DimensionMismatch(f"{name} has shape {v.shape}, expected ({self.n},)")
+        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
+        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
+        if Z.ndim != 2 or Z.shape[0] != self.n:
+            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
+        z = np.empty(self.p); beta = np.empty(self.p); se = np.empty(self.p); nlp = np.empty(self.p)
+        bf = np.empty(self.p); sf = np.empty(self.p); nf = np.empty(self.p)
+        fstate = np.empty(self.p, dtype=np.uint8)
+        fevals = np.empty(self.p, dtype=np.int32)
+        sv = np.empty(self.p) if spa else None
+        state = np.empty(self.p, dtype=np.uint8) if spa else None
+        that = np.empty((self.p, 2), order="F") if spa else None
+        _check(lib().mih_assoc_score_firth(self._h, _p(A), _p(w), _p(Z), Z.shape[1], _p(eta), float(cutoff), int(slice_rows),
+                                           _p(z), _p(beta), _p(se), _p(nlp), _p(bf), _p(sf), _p(nf), _p(fstate), _p(fevals),
+                                           _p(sv), _p(state), _p(that)))
+        return AssocResult(z, beta, se, nlp, neglog10p_spa=sv, spa_state=state, t_hat=that, beta_firth=bf, se_firth=sf,
+                           neglog10p_firth=nf, firth_state=fstate, firth_evals=fevals)
+
+    def assoc(self, y, z=None, *, d=None, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0):
         """The marginal association scan: the null model y ~ z (fit_null; z=None: an intercept) and the score test of every column
         against it.  y may be n x t for Normal traits: they share the weights, and each trait's dispersion scales its own
         statistics.  Returns an AssocResult whose `null` is the NullModel (a list of them for several traits).  spa=True (one
         Bernoulli trait, logit link): the saddlepoint p-value of the columns with |z| >= spa_cutoff beside the normal one
-        (score_test_spa)."""
+        (score_test_spa).  firth=True (likewise): the Firth-penalised effect size and likelihood-ratio p-value of the columns with
+        |z| >= firth_cutoff (score_test_firth); with spa=True too both run in one call, on one selection: spa_cutoff must then
+        equal firth_cutoff."""
         from .assoc import fit_null
         d = Normal() if d is None else _inst(d)
-        if spa:
+        if spa or firth:
+            opt = "firth=True" if firth else "spa=True"
             if not isinstance(d, Bernoulli) or (l is not None and _inst(l).code != 1):
-                raise ArgumentError("spa=True is offered for a Bernoulli trait with the logit link only, got "
+                raise ArgumentError(f"{opt} is offered for a Bernoulli trait with the logit link only, got "
                                     f"{type(d).__name__}" + ("" if l is None else f" with {type(_inst(l)).__name__}"))
+            if spa and firth and float(spa_cutoff) != float(firth_cutoff):
+                raise ArgumentError(f"spa=True with firth=True runs both passes on one selection: spa_cutoff ({spa_cutoff}) "
+                                    f"must equal firth_cutoff ({firth_cutoff})")
             y = np.asarray(y, dtype=np.float64)
             if y.ndim != 1:
-                raise ArgumentError("spa=True takes one trait")
+                raise ArgumentError(f"{opt} takes one trait")
             if y.shape[0] != self.n:
                 raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
             zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
             null = fit_null(y, zc, d, l)
-            res = self.score_test_spa(null.A, null.w, zc, null.eta, spa_cutoff, slice_rows)
+            if firth:
+                res = self.score_test_firth(null.A, null.w, zc, null.eta, firth_cutoff, slice_rows, spa=bool(spa))
+            else:
+                res = self.score_test_spa(null.A, null.w, zc, null.eta, spa_cutoff, slice_rows)
             res.null = null
             return res
         y = np.asarray(y, dtype=np.float64)
@@ -1892,29 +1932,34 @@ def iht(plinkfile, k, d, *, phenotypes=6, covariates="", summaryfile="iht.summar
 
 
 def gwas(plinkfile, d, *, phenotypes=6, covariates="", outfile="gwas.txt", exclude_std_idx=(), dosage=False, device=0,
-         two_bit=False, l=None, slice_rows=0, spa=False, spa_cutoff=2.0):
+         two_bit=False, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0):
     """The single-SNP association scan of a file, beside iht(): the inputs are parsed as iht parses them, the null model of the
     covariates is fitted (fit_null) and every SNP gets its score test (x.assoc).  outfile: `chr pos SNPid ref alt z beta se
-    neglog10p`, one row per SNP, tab-separated; spa=True (Bernoulli, logit link) adds the columns `neglog10p_spa spa_state`.
-    Returns the AssocResult."""
+    neglog10p`, one row per SNP, tab-separated; spa=True (Bernoulli, logit link) adds the columns `neglog10p_spa spa_state`,
+    firth=True (likewise) appends `beta_firth se_firth neglog10p_firth firth_state`.  Returns the AssocResult."""
     d = _inst(d)
     x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device, two_bit)
     if _is_multivariate(y):
         raise ArgumentError("gwas scans one phenotype at a time")
     if l is None:
         l = LogLink() if isinstance(d, NegativeBinomial) else canonicallink(d)
-    if spa:
+    if firth:
+        res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=bool(spa), spa_cutoff=spa_cutoff, firth=True, firth_cutoff=firth_cutoff)
+    elif spa:
         res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=True, spa_cutoff=spa_cutoff)
     else:
         res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows)
     if outfile:
         chrom, pos, ids, a1, a2 = info
         with open(outfile, "w") as f:
-            f.write("chr\tpos\tSNPid\tref\talt\tz\tbeta\tse\tneglog10p" + ("\tneglog10p_spa\tspa_state" if spa else "") + "\n")
+            f.write("chr\tpos\tSNPid\tref\talt\tz\tbeta\tse\tneglog10p" + ("\tneglog10p_spa\tspa_state" if spa else "")
+                    + ("\tbeta_firth\tse_firth\tneglog10p_firth\tfirth_state" if firth else "") + "\n")
             for j in range(x.p):
                 f.write(f"{chrom[j]}\t{pos[j]}\t{ids[j]}\t{a1[j]}\t{a2[j]}\t{float(res.z[j])!r}\t{float(res.beta[j])!r}\t"
                         f"{float(res.se[j])!r}\t{float(res.neglog10p[j])!r}"
-                        + (f"\t{float(res.neglog10p_spa[j])!r}\t{int(res.spa_state[j])}" if spa else "") + "\n")
+                        + (f"\t{float(res.neglog10p_spa[j])!r}\t{int(res.spa_state[j])}" if spa else "")
+                        + (f"\t{float(res.beta_firth[j])!r}\t{float(res.se_firth[j])!r}\t{float(res.neglog10p_firth[j])!r}\t{int(res.firth_state[j])}"
+                           if firth else "") + "\n")
     return res
 
 

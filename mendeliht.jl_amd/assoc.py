@@ -149,10 +149,16 @@ class AssocResult:
     """z, beta, neglog10p: p (one trait) or p x t; se likewise.  NaN marks a degenerate column.  null: the NullModel (a list of
     them for several Normal traits).  With the saddlepoint pass (score_test_spa, assoc(..., spa=True)): neglog10p_spa (p),
     spa_state (p, uint8: 0 not tried, 1 saddlepoint value, 2 refused -- the normal value) and t_hat (p x 2: the roots of the
-    upper and the lower tail, NaN where none); None without it."""
-    def __init__(self, z, beta, se, neglog10p, null=None, wsum=None, neglog10p_spa=None, spa_state=None, t_hat=None):
+    upper and the lower tail, NaN where none); None without it.  With the Firth pass (score_test_firth, assoc(..., firth=True)):
+    beta_firth, se_firth, neglog10p_firth (p: the penalised-likelihood estimate, its standard error and the likelihood-ratio
+    p-value; the plain values where firth_state is not 1), firth_state (p, uint8: 0 not tried, 1 penalised values, 2 refused)
+    and firth_evals (p, int32: the evaluations of the root, 0 where not tried); None without it."""
+    def __init__(self, z, beta, se, neglog10p, null=None, wsum=None, neglog10p_spa=None, spa_state=None, t_hat=None,
+                 beta_firth=None, se_firth=None, neglog10p_firth=None, firth_state=None, firth_evals=None):
         self.z, self.beta, self.se, self.neglog10p, self.null, self.wsum = z, beta, se, neglog10p, null, wsum
         self.neglog10p_spa, self.spa_state, self.t_hat = neglog10p_spa, spa_state, t_hat
+        self.beta_firth, self.se_firth, self.neglog10p_firth = beta_firth, se_firth, neglog10p_firth
+        self.firth_state, self.firth_evals = firth_state, firth_evals
 
     def top(self, k, trait=0):
         """The k columns with the largest |z| of a trait (0-based, by falling |z|; ties by index; degenerate columns never); with

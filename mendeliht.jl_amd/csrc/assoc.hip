@@ -325,19 +325,27 @@ static bool assoc_null_factor(const double *Z, const double *w, int64_t n, int c
 
 static unsigned blocks_of(int64_t items) { return (unsigned)((items + 255) / 256); }
 
-// what mih_assoc_score_spa adds to a call (nullptr: the plain scan)
+// what mih_assoc_score_spa adds to a call (nullptr: no saddlepoint pass)
 struct SpaCall { const double *eta; double cutoff; double *neglog10p_spa; uint8_t *state; double *t_hat; };
+// what mih_assoc_score_firth adds to a call (nullptr: no Firth pass); with a SpaCall beside it both passes run on one selection
+struct FirthCall { const double *eta; double cutoff; double *beta, *se, *neglog10p; uint8_t *state; int32_t *evals; };
 
-// the body of both entry points
+// the body of the three entry points
 static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
-                           double *z, double *beta, double *se, double *neglog10p, double *wsum, const SpaCall *spa)
+                           double *z, double *beta, double *se, double *neglog10p, double *wsum, const SpaCall *spa, const FirthCall *firth = nullptr)
 {
+    const char *who = firth ? "mih_assoc_score_firth" : "mih_assoc_score_spa";
     // ---- refusals: nothing allocated, nothing written ----
     if (!h || !A || !Z || !z || !beta || !se || !neglog10p) { set_error("mih_assoc_score: null argument"); return MIH_BAD_ARG; }
     if (spa) {
-        if (!w || !spa->eta || !spa->neglog10p_spa || !spa->state) { set_error("mih_assoc_score_spa: null argument"); return MIH_BAD_ARG; }
-        if (!(spa->cutoff >= 0.0)) { set_error("mih_assoc_score_spa: cutoff must not be negative or NaN, got %g", spa->cutoff); return MIH_BAD_ARG; }
+        if (!w || !spa->eta || !spa->neglog10p_spa || !spa->state) { set_error("%s: null argument", who); return MIH_BAD_ARG; }
+        if (!(spa->cutoff >= 0.0)) { set_error("%s: cutoff must not be negative or NaN, got %g", who, spa->cutoff); return MIH_BAD_ARG; }
     }
+    if (firth) {
+        if (!w || !firth->eta || !firth->beta || !firth->se || !firth->neglog10p || !firth->state) { set_error("%s: null argument", who); return MIH_BAD_ARG; }
+        if (!(firth->cutoff >= 0.0)) { set_error("%s: cutoff must not be negative or NaN, got %g", who, firth->cutoff); return MIH_BAD_ARG; }
+    }
+    const double *eta = firth ? firth->eta : spa ? spa->eta : nullptr;
     if (t < 1 || t > 32) { set_error("mih_assoc_score: 1 <= t <= 32 traits, got %d", (int)t); return MIH_BAD_ARG; }
     if (c < 1 || c > 64) { set_error("mih_assoc_score: 1 <= c <= 64 covariates, got %d", (int)c); return MIH_BAD_ARG; }
     if (slice_rows < 0) { set_error("mih_assoc_score: slice_rows must not be negative, got %lld", (long long)slice_rows); return MIH_BAD_ARG; }
@@ -351,7 +359,7 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         }
     if (!all_finite(A, (size_t)n * (size_t)t)) { set_error("mih_assoc_score: a score residual is not finite"); return MIH_BAD_ARG; }
     if (!all_finite(Z, (size_t)n * (size_t)c)) { set_error("mih_assoc_score: a covariate is not finite"); return MIH_BAD_ARG; }
-    if (spa && !all_finite(spa->eta, (size_t)n)) { set_error("mih_assoc_score_spa: a linear predictor is not finite"); return MIH_BAD_ARG; }
+    if (eta && !all_finite(eta, (size_t)n)) { set_error("%s: a linear predictor is not finite", who); return MIH_BAD_ARG; }
     std::vector<double> Linv;
     if (!assoc_null_factor(Z, w, n, c, Linv)) { set_error("mih_assoc_score: Z'WZ is not positive definite"); return MIH_BAD_ARG; }
 
@@ -385,10 +393,18 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         need += ops * (double)nblk * 64.0 * 24.0 + 16.0 * m * (double)ncg * 32.0 * 8.0 + 32.0 * dp;      // the fused pass's digit planes and partial sums; Wc
         if (classes) need += 8.0 * (double)h->n_pad + (double)nblk * 1024.0 + (double)nsl * (double)ncg * 8192.0 + 16.0 * dp;   // R_i, their digit planes, the integer partials, Tm
     }
-    const double need_spa = spa ? assoc_spa_bytes(n, p, (int)c) : 0.0;
-    need += need_spa;
+    // the selection, alpha and the slabs are held once, whichever passes run on them
+    const double need_spa = spa ? assoc_spa_bytes(n, p, (int)c) : firth ? assoc_flag_bytes(n, p, (int)c) : 0.0;
+    const double need_firth = firth ? assoc_firth_bytes(p) : 0.0;
+    need += need_spa + need_firth;
     size_t free_b = 0, total_b = 0;
     MIH_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (firth && need > (double)free_b) {
+        set_error("mih_assoc_score_firth: the scan needs %.0f bytes of device memory, the selection %.0f more (the linear predictor, the flagged columns' alpha%s, %lld slabs of %lld adjusted genotypes, held once) and the Firth pass %.0f more (the roots of up to %lld columns), %.0f bytes are free",
+                  need - need_spa - need_firth, need_spa, spa ? " and saddlepoint tails" : "", (long long)std::min<int64_t>(p, kSpaSlabs), (long long)n, need_firth,
+                  (long long)p, (double)free_b);
+        return MIH_OOM;
+    }
     if (spa && need > (double)free_b) {
         set_error("mih_assoc_score_spa: the scan needs %.0f bytes of device memory and the saddlepoint pass %.0f more (the linear predictor, the flagged columns' alpha and tails, %lld slabs of %lld adjusted genotypes), %.0f bytes are free",
                   need - need_spa, need_spa, (long long)std::min<int64_t>(p, kSpaSlabs), (long long)n, (double)free_b);
@@ -499,10 +515,16 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         MIH_HIP(hipMemcpyAsync(hw.data(), Wc.p, sizeof(double) * (size_t)(4 * p), hipMemcpyDeviceToHost, s));
     }
     MIH_HIP(hipStreamSynchronize(s));
-    std::vector<double> hn(hz.size()), spa_v, spa_t;
-    std::vector<uint8_t> spa_s;
+    std::vector<double> hn(hz.size()), spa_v, spa_t, f_b, f_se, f_n;
+    std::vector<uint8_t> spa_s, f_s;
+    std::vector<int32_t> f_e;
     for (size_t i = 0; i < hz.size(); ++i) hn[i] = neglog10p_of_z(hz[i]);
-    if (spa) MIH_TRY(assoc_spa_run(h, s, (int)c, S.p, V.p, zd.p, Ld.p, Zd.p, spa->eta, spa->cutoff, hn.data(), spa_v, spa_s, spa_t));
+    if (spa || firth) {
+        AssocFlagged fl;
+        MIH_TRY(assoc_flag_run(who, h, s, (int)c, S.p, zd.p, Ld.p, eta, firth ? firth->cutoff : spa->cutoff, fl));
+        if (spa) MIH_TRY(assoc_spa_run(h, s, (int)c, fl, S.p, V.p, Zd.p, hn.data(), spa_v, spa_s, spa_t));
+        if (firth) MIH_TRY(assoc_firth_run(h, s, (int)c, fl, S.p, V.p, Zd.p, hb.data(), hs.data(), hn.data(), f_b, f_se, f_n, f_s, f_e));
+    }
     memcpy(z, hz.data(), sizeof(double) * hz.size());
     memcpy(beta, hb.data(), sizeof(double) * hb.size());
     memcpy(se, hs.data(), sizeof(double) * hs.size());
@@ -511,6 +533,13 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         memcpy(spa->neglog10p_spa, spa_v.data(), sizeof(double) * spa_v.size());
         memcpy(spa->state, spa_s.data(), spa_s.size());
         if (spa->t_hat) memcpy(spa->t_hat, spa_t.data(), sizeof(double) * spa_t.size());
+    }
+    if (firth) {
+        memcpy(firth->beta, f_b.data(), sizeof(double) * f_b.size());
+        memcpy(firth->se, f_se.data(), sizeof(double) * f_se.size());
+        memcpy(firth->neglog10p, f_n.data(), sizeof(double) * f_n.size());
+        memcpy(firth->state, f_s.data(), f_s.size());
+        if (firth->evals) memcpy(firth->evals, f_e.data(), sizeof(int32_t) * f_e.size());
     }
     if (wsum)
         for (int64_t j = 0; j < p; ++j)
@@ -536,6 +565,16 @@ int mih_assoc_score_spa(const mih_mat *h, const double *A, const double *w, cons
 {
     const SpaCall spa = {eta, cutoff, neglog10p_spa, state, t_hat};
     return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, &spa);
+}
+
+int mih_assoc_score_firth(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, const double *eta, double cutoff,
+                          int64_t slice_rows, double *z, double *beta, double *se, double *neglog10p, double *beta_firth, double *se_firth,
+                          double *neglog10p_firth, uint8_t *firth_state, int32_t *firth_evals, double *neglog10p_spa, uint8_t *spa_state,
+                          double *t_hat)
+{
+    const FirthCall firth = {eta, cutoff, beta_firth, se_firth, neglog10p_firth, firth_state, firth_evals};
+    const SpaCall spa = {eta, cutoff, neglog10p_spa, spa_state, t_hat};
+    return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, neglog10p_spa ? &spa : nullptr, &firth);
 }
 
 }  // extern "C"

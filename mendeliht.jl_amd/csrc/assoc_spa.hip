@@ -20,57 +20,15 @@
 // workgroup and U, b, V are bit-reproducible, so neglog10p_spa, state and t_hat are bit for bit the same whatever slice_rows
 // and the number of workgroups, and on repeated calls.  The loop's control values (SpaIter) live in registers: every lane reads
 // the same two sums from LDS and makes the same step.
+//
+// The slab's formation, the tree and the pass over the rows live in assoc_slab.h, one copy for this kernel and k_assoc_firth;
+// the selection, alpha and the slabs (assoc_flag_run) serve both passes of a call that asks for both.
 #include "assoc_spa.h"
 #include <cmath>
 #include <limits>
 #include <vector>
 
 namespace mih {
-
-__device__ __forceinline__ void spa_tree(double (*red)[256], int nv)
-{
-#pragma clang fp contract(off)
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k)
-            for (int v = 0; v < nv; ++v) red[v][threadIdx.x] = red[v][threadIdx.x] + red[v][threadIdx.x + k];
-        __syncthreads();
-    }
-}
-
-// One pass over the rows of a column at argument t, the thread's rows tid, tid + 256, ... in ascending order:
-//   ROOT = false:  a = sum c_i (sigma(x_i) - aux_i),  aux = mu            b = sum c_i^2 sigma(x_i) (1 - sigma(x_i))
-//   ROOT = true:   a = sum (softplus(x_i) - aux_i),   aux = softplus(eta)  b likewise
-// x_i = eta_i + c_i t.  The loads of kSpaAhead rows are issued before the first of them is used (a pass is bound by the latency
-// of its loads otherwise: one row per thread in flight); the terms are added in row order all the same, so the sums do not
-// depend on it.
-constexpr int kSpaAhead = 4;
-
-template <bool ROOT>
-__device__ __forceinline__ void spa_term(double cc, double h, double aux, double t, double &a, double &b)
-{
-#pragma clang fp contract(off)
-    const double x = h + cc * t, e = exp(-fabs(x)), r = 1.0 / (1.0 + e), er = e * r;
-    if (ROOT) a = a + ((fmax(x, 0.0) + log1p(e)) - aux);
-    else a = a + cc * ((x >= 0.0 ? r : er) - aux);
-    b = b + (cc * cc) * (er * r);
-}
-
-template <bool ROOT>
-__device__ __forceinline__ void spa_pass(const double *cs, const double *__restrict__ eta, const double *__restrict__ aux,
-                                         int64_t n, double t, double &a, double &b)
-{
-    a = 0.0; b = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 256 * (kSpaAhead - 1) < n; i += 256 * kSpaAhead) {
-        double cc[kSpaAhead], h[kSpaAhead], ax[kSpaAhead];
-        #pragma unroll
-        for (int u = 0; u < kSpaAhead; ++u) { cc[u] = cs[i + 256 * u]; h[u] = eta[i + 256 * u]; ax[u] = aux[i + 256 * u]; }
-        #pragma unroll
-        for (int u = 0; u < kSpaAhead; ++u) spa_term<ROOT>(cc[u], h[u], ax[u], t, a, b);
-    }
-    for (; i < n; i += 256) spa_term<ROOT>(cs[i], eta[i], aux[i], t, a, b);
-}
 
 // per row: mu_i = sigma(eta_i) and softplus(eta_i), by the expressions of the evaluations (so that every term of K'(0) is 0)
 __global__ void __launch_bounds__(256)
@@ -131,12 +89,6 @@ k_assoc_spa_alpha(const double *__restrict__ S, int64_t p, int c, const double *
     }
 }
 
-struct SpaMat {
-    const double *D; const float *Df; DosageView dv;
-    const uint32_t *X; int64_t nbp; const double *mu, *sinv; int center, scale, impute;
-    const int64_t *miss_ptr; const int32_t *miss_row;
-};
-
 // The solve.  rec[8 f ..] = q, V, then t_hat, K(t_hat), K''(t_hat) of tail 0 (target +|q|) and of tail 1 (-|q|); st[4 f ..] =
 // status and evaluations of tail 0, of tail 1 (SpaTail).  slab: gridDim.x x n doubles.
 template <int KIND>      // 0: f64, 1: f32, 2: dosage, 3: 2-bit
@@ -155,32 +107,8 @@ k_assoc_spa(SpaMat m, int64_t n, int64_t p, int c, const int64_t *__restrict__ i
         const int64_t j = idx[f];
         __syncthreads();                                     // the last column's reads of al and red are over
         if (tid < c) al[tid] = alpha[f * c + tid];
-        if (KIND == 3) {                                     // the stored codes first, then the column's missing rows over them
-            const double s = m.scale ? m.sinv[j] : 1.0, cm = m.center ? m.mu[j] : 0.0;
-            const double x0 = (0.0 - cm) * s, x1 = (1.0 - cm) * s, x2 = (2.0 - cm) * s, xm = ((m.impute ? m.mu[j] : 0.0) - cm) * s;
-            for (int64_t i = tid; i < n; i += 256) {
-                const uint32_t g = (m.X[xword(m.nbp, j, i >> 4)] >> (2 * (int)(i & 15))) & 3u;
-                cs[i] = g == 0u ? x0 : g == 1u ? x1 : x2;
-            }
-            __syncthreads();
-            for (int64_t e = m.miss_ptr[j] + tid, e1 = m.miss_ptr[j + 1]; e < e1; e += 256) {
-                const int64_t row = m.miss_row[e];
-                if (row >= 0 && row < n) cs[row] = xm;
-            }
-        }
-        __syncthreads();
-        // c_i, M1 = sum c_i mu_i and the two ends of the range
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-        for (int64_t i = tid; i < n; i += 256) {
-            const double x = KIND == 0 ? m.D[j * n + i] : KIND == 1 ? (double)m.Df[j * n + i] : KIND == 2 ? dosage_x(m.dv, j, i) : cs[i];
-            double za = 0.0;
-            for (int k = 0; k < c; ++k) za = za + Z[(int64_t)k * n + i] * al[k];
-            const double cc = x - za;
-            cs[i] = cc;
-            a0 = a0 + cc * mu[i];
-            a1 = a1 + fmin(cc, 0.0);
-            a2 = a2 + fmax(cc, 0.0);
-        }
+        double a0, a1, a2;
+        spa_slab_form<KIND>(m, n, j, c, al, Z, mu, cs, a0, a1, a2);
         red[0][tid] = a0; red[1][tid] = a1; red[2][tid] = a2;
         spa_tree(red, 3);
         const double m1 = red[0][0], smin = red[1][0] - m1, smax = red[2][0] - m1;
@@ -225,50 +153,73 @@ k_assoc_spa(SpaMat m, int64_t n, int64_t p, int c, const int64_t *__restrict__ i
     }
 }
 
-double assoc_spa_bytes(int64_t n, int64_t p, int c)
+double assoc_flag_bytes(int64_t n, int64_t p, int c)
 {
     const double dn = (double)n, dp = (double)p;
     return 8.0 * 3.0 * dn                                    // eta, mu, softplus(eta)
          + 8.0 * (dp + 1.0)                                  // the flagged columns' indices and their count
-         + dp * (8.0 * c + 64.0 + 16.0)                      // alpha, the tails' values and their status words, had every column been flagged
+         + dp * (8.0 * c)                                    // alpha, had every column been flagged
          + 8.0 * dn * (double)std::min<int64_t>(p, kSpaSlabs);      // the slabs of c_i
 }
 
-int assoc_spa_run(const mih_mat *h, hipStream_t s, int c, const double *S, const double *V, const double *z, const double *Linv,
-                  const double *Z, const double *eta_host, double cutoff, const double *nlp, std::vector<double> &out,
-                  std::vector<uint8_t> &state, std::vector<double> &that)
+double assoc_spa_bytes(int64_t n, int64_t p, int c)
+{
+    return assoc_flag_bytes(n, p, c) + (double)p * (64.0 + 16.0);   // the tails' values and their status words, had every column been flagged
+}
+
+int assoc_flag_run(const char *who, const mih_mat *h, hipStream_t s, int c, const double *S, const double *z, const double *Linv,
+                   const double *eta_host, double cutoff, AssocFlagged &fl)
 {
     const int64_t n = h->n, p = h->p;
-    out.assign(nlp, nlp + p);
-    state.assign((size_t)p, 0);
-    that.assign((size_t)(2 * p), std::numeric_limits<double>::quiet_NaN());
-    DevBuf<int64_t> idx;
-    MIH_TRY(idx.alloc((size_t)p + 1));
-    hipLaunchKernelGGL(k_assoc_spa_select, dim3(1), dim3(256), 0, s, z, p, cutoff, idx.p);
+    fl.nflag = 0; fl.grid = 0;
+    MIH_TRY(fl.idx.alloc((size_t)p + 1));
+    hipLaunchKernelGGL(k_assoc_spa_select, dim3(1), dim3(256), 0, s, z, p, cutoff, fl.idx.p);
     MIH_TRY(launch_failed("k_assoc_spa_select"));
     int64_t nflag = 0;
-    MIH_HIP(hipMemcpyAsync(&nflag, idx.p + p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    MIH_HIP(hipMemcpyAsync(&nflag, fl.idx.p + p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     MIH_HIP(hipStreamSynchronize(s));
-    if (nflag < 0 || nflag > p) { set_error("mih_assoc_score_spa: the selection counted %lld of %lld columns", (long long)nflag, (long long)p); return MIH_HIP_ERROR; }
+    if (nflag < 0 || nflag > p) { set_error("%s: the selection counted %lld of %lld columns", who, (long long)nflag, (long long)p); return MIH_HIP_ERROR; }
     if (nflag == 0) return MIH_OK;
 
     const int64_t grid = std::min(nflag, kSpaSlabs);
-    DevBuf<double> etad, mud, sp0d, alpha, slab, rec;
-    DevBuf<int32_t> st;
-    MIH_TRY(etad.alloc((size_t)n)); MIH_TRY(mud.alloc((size_t)n)); MIH_TRY(sp0d.alloc((size_t)n));
-    MIH_TRY(alpha.alloc((size_t)(nflag * c))); MIH_TRY(slab.alloc((size_t)(grid * n)));
-    MIH_TRY(rec.alloc((size_t)(8 * nflag))); MIH_TRY(st.alloc((size_t)(4 * nflag)));
-    MIH_HIP(hipMemcpyAsync(etad.p, eta_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_assoc_spa_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, etad.p, n, mud.p, sp0d.p);
+    MIH_TRY(fl.eta.alloc((size_t)n)); MIH_TRY(fl.mu.alloc((size_t)n)); MIH_TRY(fl.sp0.alloc((size_t)n));
+    MIH_TRY(fl.alpha.alloc((size_t)(nflag * c))); MIH_TRY(fl.slab.alloc((size_t)(grid * n)));
+    MIH_HIP(hipMemcpyAsync(fl.eta.p, eta_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_assoc_spa_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fl.eta.p, n, fl.mu.p, fl.sp0.p);
     MIH_TRY(launch_failed("k_assoc_spa_rows"));
-    hipLaunchKernelGGL(k_assoc_spa_alpha, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, s, S, p, c, Linv, idx.p, nflag, alpha.p);
+    hipLaunchKernelGGL(k_assoc_spa_alpha, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, s, S, p, c, Linv, fl.idx.p, nflag, fl.alpha.p);
     MIH_TRY(launch_failed("k_assoc_spa_alpha"));
+    fl.hidx.resize((size_t)nflag);
+    MIH_HIP(hipMemcpyAsync(fl.hidx.data(), fl.idx.p, sizeof(int64_t) * (size_t)nflag, hipMemcpyDeviceToHost, s));
+    MIH_HIP(hipStreamSynchronize(s));
+    for (int64_t f = 0; f < nflag; ++f)
+        if (fl.hidx[(size_t)f] < 0 || fl.hidx[(size_t)f] >= p) { set_error("%s: flagged column %lld of %lld", who, (long long)fl.hidx[(size_t)f], (long long)p); return MIH_HIP_ERROR; }
+    fl.nflag = nflag; fl.grid = grid;
+    return MIH_OK;
+}
 
-    SpaMat m = {h->D, h->Df, dosage_view(h), h->X, h->nbp, h->mu, h->sinv, h->center, h->scale, h->impute, h->miss_ptr, h->miss_row};
+SpaMat assoc_spa_mat(const mih_mat *h)
+{
+    return SpaMat{h->D, h->Df, dosage_view(h), h->X, h->nbp, h->mu, h->sinv, h->center, h->scale, h->impute, h->miss_ptr, h->miss_row};
+}
+
+int assoc_spa_run(const mih_mat *h, hipStream_t s, int c, const AssocFlagged &fl, const double *S, const double *V, const double *Z,
+                  const double *nlp, std::vector<double> &out, std::vector<uint8_t> &state, std::vector<double> &that)
+{
+    const int64_t n = h->n, p = h->p, nflag = fl.nflag, grid = fl.grid;
+    out.assign(nlp, nlp + p);
+    state.assign((size_t)p, 0);
+    that.assign((size_t)(2 * p), std::numeric_limits<double>::quiet_NaN());
+    if (nflag == 0) return MIH_OK;
+
+    DevBuf<double> rec;
+    DevBuf<int32_t> st;
+    MIH_TRY(rec.alloc((size_t)(8 * nflag))); MIH_TRY(st.alloc((size_t)(4 * nflag)));
+    SpaMat m = assoc_spa_mat(h);
     PassRecord pr;
     const bool timed = prof_begin(h, s, pr);
-#define MIH_SPA_LAUNCH(KIND) hipLaunchKernelGGL(k_assoc_spa<KIND>, dim3((unsigned)grid), dim3(256), 0, s, m, n, p, c, idx.p, nflag, alpha.p, Z, \
-                                                etad.p, mud.p, sp0d.p, S, V, slab.p, rec.p, st.p)
+#define MIH_SPA_LAUNCH(KIND) hipLaunchKernelGGL(k_assoc_spa<KIND>, dim3((unsigned)grid), dim3(256), 0, s, m, n, p, c, fl.idx.p, nflag, fl.alpha.p, Z, \
+                                                fl.eta.p, fl.mu.p, fl.sp0.p, S, V, fl.slab.p, rec.p, st.p)
     if (h->kind == 0) MIH_SPA_LAUNCH(3);
     else if (h->Du) MIH_SPA_LAUNCH(2);
     else if (h->Df) MIH_SPA_LAUNCH(1);
@@ -277,18 +228,15 @@ int assoc_spa_run(const mih_mat *h, hipStream_t s, int c, const double *S, const
     if (timed) { snprintf(pr.kernel, sizeof(pr.kernel), "k_assoc_spa"); pr.residuals = 1; pr.operands = (int)std::min<int64_t>(nflag, 2147483647); prof_end(h, s, pr); }
     MIH_TRY(launch_failed("k_assoc_spa"));
 
-    std::vector<int64_t> hidx((size_t)nflag);
     std::vector<double> hrec((size_t)(8 * nflag));
     std::vector<int32_t> hst((size_t)(4 * nflag));
-    MIH_HIP(hipMemcpyAsync(hidx.data(), idx.p, sizeof(int64_t) * (size_t)nflag, hipMemcpyDeviceToHost, s));
     MIH_HIP(hipMemcpyAsync(hrec.data(), rec.p, sizeof(double) * hrec.size(), hipMemcpyDeviceToHost, s));
     MIH_HIP(hipMemcpyAsync(hst.data(), st.p, sizeof(int32_t) * hst.size(), hipMemcpyDeviceToHost, s));
     MIH_HIP(hipStreamSynchronize(s));
 
     int64_t tails = 0, evals = 0;
     for (int64_t f = 0; f < nflag; ++f) {
-        const int64_t j = hidx[(size_t)f];
-        if (j < 0 || j >= p) { set_error("mih_assoc_score_spa: flagged column %lld of %lld", (long long)j, (long long)p); return MIH_HIP_ERROR; }
+        const int64_t j = fl.hidx[(size_t)f];
         const double *r = &hrec[(size_t)(8 * f)];
         const int32_t *w = &hst[(size_t)(4 * f)];
         SpaTail tl[2];
