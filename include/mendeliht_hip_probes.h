@@ -4,7 +4,8 @@
  * tools/ and the "this switch changes nothing" tests use them to sweep launch shapes, to cross-check the product's
  * kernels bit for bit against the round-1 kernel families, to run timing probes, and to drive sequences of calls on ONE
  * workspace (mih_probe_xtv_sequence: fused X'r passes; mih_probe_xv_sequence: the cached and multi-trait X beta paths of a
- * fit), and to run the GLM refit of debias! on its own (mih_probe_debias_glm).  The measurement build also reads
+ * fit), to run the GLM refit of debias! on its own (mih_probe_debias_glm) and the initialize_beta! regressions on their own
+ * (mih_probe_init_beta).  The measurement build also reads
  * the MENDELIHT_* A/B environment switches (XTV_MAX_OPS, XTV_SLICES, XTV_NO_HALF, CV_LANES, CV_NO_MERGE,
  * CV_NO_INIT_SHARE, CV_NO_COOP, COOP_SPIN_US, CV_TRACE, INGEST_TRACE, INGEST_THREADS, TRACE_ETA, NO_SPIN, NO_ARENA, NO_RESERVE,
  * NO_RESIDENT, TOPK_RADIX8, XV_MULTI, RES_FORCE_ABORT_ES, DEBIAS_TRACE = the IRLS iterates of debias!'s GLM refit on stderr); the
@@ -53,6 +54,17 @@ int mih_probe_xv_sequence(const mih_mat *h, int64_t max_nnz, int64_t cache_nnz, 
  * from a fit. */
 int mih_probe_debias_glm(const mih_mat *h, const int64_t *idx, int64_t k, const double *y, int dist, int link, double nb_r,
                          double *beta, double *gram0, double *w0, double *t0, int32_t *irls_iters);
+/* The p univariate regressions y_t ~ 1 + x_j of initialize_beta! (csrc/iht_var.hip: init_beta_regress_device, what every fit with
+ * init_beta calls) on their own, on the matrix's stream, for m traits (1 <= m <= 32): w (n doubles on the host, each 0.0 = held out
+ * or 1.0 = training row) and Y (n x m, column-major) are uploaded; N and Sy[t] = sum of Y[., t] over the training rows are summed
+ * on the host in row order as a fit sums them.  BETA (m x p, plane t = trait t): the slopes clamped to [-2, 2].  The other outputs
+ * (each may be null) are the intermediates: S ((1 + m) x p: row 0 = sum_train x_j, row 1 + t = sum_train x_j y_t, the fused X'R
+ * pass), CNT (2p, 2-bit handles only, ignored otherwise: CNT[2j + k] = training rows of column j with dosage k + 1), SXX (p, dense
+ * and dosage handles only, ignored for 2-bit ones: sum_train x_j^2), ICPT (m x p: the intercepts, or the unsolved sum y where
+ * N sxx - sx^2 is not positive) and ICPT_SUM (m: the device's sum of each ICPT plane).  MIH_BAD_ARG, before any launch and with no
+ * output written, for a null h, w, Y or beta, m outside 1..32, a w entry that is neither 0 nor 1, no training row, a non-finite Y. */
+int mih_probe_init_beta(const mih_mat *h, const double *w, const double *Y, int m, double *S, int32_t *cnt, double *sxx,
+                        double *beta, double *icpt, double *icpt_sum);
 #ifdef __cplusplus
 }
 #endif

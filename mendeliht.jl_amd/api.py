@@ -225,7 +225,8 @@ def lib():
                     "mih_probe_set_max_fused": [C.c_int],
                     "mih_probe_xtv_sequence": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
                     "mih_probe_xv_sequence": [vp, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp],
-                    "mih_probe_debias_glm": [vp, vp, i64, vp, C.c_int, C.c_int, dbl, vp, vp, vp, vp, vp]})
+                    "mih_probe_debias_glm": [vp, vp, i64, vp, C.c_int, C.c_int, dbl, vp, vp, vp, vp, vp],
+                    "mih_probe_init_beta": [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]})
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
@@ -255,7 +256,7 @@ def exported_symbols():
 def probe_symbols():
     """What include/mendeliht_hip_probes.h declares: exported by the measurement build only."""
     return ["mih_probe_set_xtv_variant", "mih_probe_set_xtv_multi_variant", "mih_probe_set_max_fused", "mih_probe_xtv_sequence",
-            "mih_probe_xv_sequence", "mih_probe_debias_glm"]
+            "mih_probe_xv_sequence", "mih_probe_debias_glm", "mih_probe_init_beta"]
 
 
 def _check(rc):

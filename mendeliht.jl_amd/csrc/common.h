@@ -614,8 +614,13 @@ bool comm_is_native(const mih_comm *c, int device);       // the library's own R
 // rank_of[fold * npath + ik]: which rank of `world` evaluates that (fold, k) combination (mih_cv_assignment; fit_lockstep.hip)
 void cv_assign(const int64_t *path, int64_t npath, int32_t nfolds, int32_t world, std::vector<int32_t> &rank_of);
 // initialize_beta! regressions for m response planes (iht_var.hip); shared by the univariate and multivariate fits
+// IbCapture (mih_probe_init_beta only; the fits pass none): host destinations, each may be null, for the intermediates -- the X'R
+// result S ((1 + m) x p), the 2-bit dosage counts (2p), the dense / dosage sum of squares (p) and the m intercept planes (m x p,
+// plane t copied before trait t + 1 overwrites the device buffer).  Without one the function queues nothing extra.
+struct IbCapture { double *S = nullptr; int32_t *cnt = nullptr; double *sxx = nullptr; double *icpt = nullptr; };
 int  init_beta_regress_device(const mih_mat *h, const double *w_dev, const double *Y_dev, int m, double N,
                               const double *Sy_host, double *beta_dev, double *icpt_sum_host,
-                              DevBuf<double> &red, DevBuf<double> &scal, hipStream_t s, const XtvTune &tune);
+                              DevBuf<double> &red, DevBuf<double> &scal, hipStream_t s, const XtvTune &tune,
+                              const IbCapture *cap = nullptr);
 
 }  // namespace mih

@@ -378,7 +378,7 @@ static double h_mueta(int link, double eta)
 
 int init_beta_regress_device(const mih_mat *h, const double *w_dev, const double *Y_dev, int m, double N,
                              const double *Sy_host, double *beta_dev, double *icpt_sum_host,
-                             DevBuf<double> &red, DevBuf<double> &scal, hipStream_t s, const XtvTune &tune)
+                             DevBuf<double> &red, DevBuf<double> &scal, hipStream_t s, const XtvTune &tune, const IbCapture *cap)
 {
     const int64_t n = h->n, p = h->p;
     XtvWork xw; DevBuf<double> R, S, icpt, sxxd; DevBuf<uint32_t> M; DevBuf<int32_t> cnt;
@@ -408,6 +408,12 @@ int init_beta_regress_device(const mih_mat *h, const double *w_dev, const double
         hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(256), 0, s, red.p, nsb, 1, scal.p);
         MIH_HIP(hipMemcpyAsync(&icpt_sum_host[t], scal.p, sizeof(double), hipMemcpyDeviceToHost, s));
         MIH_HIP(hipStreamSynchronize(s));
+        if (cap && cap->icpt) MIH_HIP(hipMemcpy(cap->icpt + (size_t)t * p, icpt.p, sizeof(double) * p, hipMemcpyDeviceToHost));
+    }
+    if (cap) {                                    // (the loop's last synchronize has drained the stream)
+        if (cap->S) MIH_HIP(hipMemcpy(cap->S, S.p, sizeof(double) * (size_t)(1 + m) * p, hipMemcpyDeviceToHost));
+        if (cap->cnt && h->kind == 0) MIH_HIP(hipMemcpy(cap->cnt, cnt.p, sizeof(int32_t) * 2 * p, hipMemcpyDeviceToHost));
+        if (cap->sxx && h->kind != 0) MIH_HIP(hipMemcpy(cap->sxx, sxxd.p, sizeof(double) * p, hipMemcpyDeviceToHost));
     }
     return MIH_OK;
 }
@@ -1964,3 +1970,45 @@ int check_params(const mih_mat *h, const mih_fit_params *prm, int64_t q)
 }
 
 }  // namespace mih
+
+#ifdef MIH_PROBES
+// include/mendeliht_hip_probes.h: the initialize_beta! regressions on their own, on the matrix's stream, with their intermediates.
+// N and Sy are summed over the training rows in row order, as IhtVar::init_beta_phase sums them; every refusal is decided here,
+// before a launch.
+extern "C" int mih_probe_init_beta(const mih_mat *h, const double *w, const double *Y, int m, double *S, int32_t *cnt, double *sxx,
+                                   double *beta, double *icpt, double *icpt_sum)
+{
+    using namespace mih;
+    if (!h || !w || !Y || !beta) { set_error("null argument"); return MIH_BAD_ARG; }
+    if (m < 1 || m > 32) { set_error("m = %d traits must be in 1..32", m); return MIH_BAD_ARG; }
+    const int64_t n = h->n, p = h->p;
+    double N = 0.0;
+    std::vector<double> Sy(m, 0.0), c0sum(m, 0.0);
+    for (int64_t i = 0; i < n; ++i) {
+        if (w[i] != 0.0 && w[i] != 1.0) { set_error("w[%lld] is neither 0 nor 1", (long long)i); return MIH_BAD_ARG; }
+        if (w[i] != 0.0) N += 1.0;
+    }
+    if (!(N > 0.0)) { set_error("no training row"); return MIH_BAD_ARG; }
+    for (int t = 0; t < m; ++t)
+        for (int64_t i = 0; i < n; ++i) {
+            const double yv = Y[(size_t)t * n + i];
+            if (!std::isfinite(yv)) { set_error("Y[%lld, %d] is not finite", (long long)i, t); return MIH_BAD_ARG; }
+            if (w[i] != 0.0) Sy[t] += yv;
+        }
+    MIH_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DevBuf<double> wd, Yd, betad, red, scal;
+    MIH_TRY(wd.alloc((size_t)n)); MIH_TRY(Yd.alloc((size_t)m * n)); MIH_TRY(betad.alloc((size_t)m * p));
+    MIH_TRY(red.alloc(64)); MIH_TRY(scal.alloc(4));
+    MIH_HIP(hipMemcpyAsync(wd.p, w, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    MIH_HIP(hipMemcpyAsync(Yd.p, Y, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
+    IbCapture cap;
+    cap.S = S; cap.cnt = cnt; cap.sxx = sxx; cap.icpt = icpt;
+    const int rc = init_beta_regress_device(h, wd.p, Yd.p, m, N, Sy.data(), betad.p, c0sum.data(), red, scal, s, xtv_tune(0), &cap);
+    (void)hipStreamSynchronize(s);
+    if (rc != MIH_OK) return rc;
+    MIH_HIP(hipMemcpy(beta, betad.p, sizeof(double) * (size_t)m * p, hipMemcpyDeviceToHost));
+    if (icpt_sum) std::copy(c0sum.begin(), c0sum.end(), icpt_sum);
+    return MIH_OK;
+}
+#endif

@@ -207,8 +207,9 @@ def brute(X, A, w, Z):
 def _xtv_bound_snp(codes, flags, stats, R):
     """|X'r_device - X'r| per column and residual (p x m) for a 2-bit handle: the bound tests/test_gpu_xtv_residual_edges.py holds
     X'r to (gpu_helpers.xtv_edge_exact / xtv_matrix_exact / xtv_std_exact), restated in floats for the fused default format:
-        |sinv_j| ( (q / 2) sum_i g_ij [row i not peeled] + C u D_j + u [ (k_j - 1) M_j + (ceil(n / 16384) + 70) S_j + 6 (D_j + M_j + S_j) ] )
-    q = xtv_quantum(r), C = xtv_recombine_count(None, 16) (the largest slice count), D_j = sum_i g_ij |r_i|, M_j = [impute] |mu_j|
+        |sinv_j| ( (q / 2) sum_i g_ij [row i not peeled, r_i != 0] + C u D_j + u [ (k_j - 1) M_j + (ceil(n / 16384) + 70) S_j + 6 (D_j + M_j + S_j) ] )
+    (a residual that is exactly 0 has the fixed-point value 0: no quantisation error; a train mask that leaves few rows has every
+    non-zero row peeled, and the term vanishes), q = xtv_quantum(r), C = xtv_recombine_count(None, 16) (the largest slice count), D_j = sum_i g_ij |r_i|, M_j = [impute] |mu_j|
     sum_{i missing} |r_i|, S_j = [center] |mu_j| sum_i |r_i|, k_j the column's missing entries."""
     import gpu_helpers as H
     center, scale, impute = flags
@@ -226,6 +227,7 @@ def _xtv_bound_snp(codes, flags, stats, R):
         q = H.xtv_quantum(r, None)
         inside = np.ones(n)
         inside[H.peel_rule(r)] = 0.0
+        inside[r == 0.0] = 0.0
         ar = np.abs(r)
         D = g.T @ ar
         M = amu * (miss.T @ ar) if impute else np.zeros(p)
