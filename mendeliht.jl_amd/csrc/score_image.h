@@ -102,6 +102,166 @@ struct HomSum {
 };
 MIH_HD uint64_t hom_u(long long R) { return (uint64_t)R + 0x00AAAAAAAAAAAAAAull; }
 
+// The same sums by counting bit positions (what k_xtv_hom runs; HomSum above is the plain statement it is held to).  With C[b] the
+// number of terms whose U has bit b set, sum u_t = C[2t] + 2 C[2t + 1]: a word whose bit b is a count's bit of weight v, read as
+// 2-bit fields, is a word of digit sums of weight v.  The counts are kept bit-sliced on the two 32-bit halves w of U (as above):
+//   s[v][w], v = 0..4   bit b = bit v of C[32w + b] (weights 1, 2, 4, 8, 16), by carry-save adders -- csa(): three operations, two on gfx950;
+//   chunk_carry()       a chunk's 8 words into s[0..2] with 7 adders a half; what comes out is one carry word of weight 8;
+//   pair_carry()        the carry words of two consecutive chunks into s[3]: one carry word of weight 16;
+//   add_pairs()         the carry words of two consecutive pairs into s[4]: one carry word of weight 32 per group of kCsaGroup = 4
+//                       chunks, whose 2-bit fields go to the 4-bit fields f[c][w] += (carry >> 2c) & 0x33333333 (digit
+//                       16w + 2j + c in field j);
+//   flush()             the 4-bit fields, times 32, into the 32-bit counters cnt[].  A field gains at most 3 per carry word:
+//                       flush() runs BEFORE the carry word that would be the (kCsaFlush + 1)-th since the last one;
+//   finish()            the planes into cnt[] as well, once per list: per half and j, sum_v ((s[v][w] >> 2j) & 0x03030303) << v has
+//                       digit 16w + 4i + j in byte i, at most 3 * 31 = 93.
+// A chunk that is missing from a pair or a group is a zero carry word: it adds nothing and is no term.  A list's padding entry
+// (U of R = 0) is a term.  Every plane is a count modulo 32, and cnt[t] <= 3 * 2^22 < 2^24 for the 2^22 terms a lane can see in a
+// slice.
+constexpr int kCsaGroup = 4;          // chunks per carry word of weight 32: 4 * kHomChunk = 32 terms
+constexpr int kCsaFlush = 5;          // carry words between two flush(): 5 * 3 = 15 fits a 4-bit field, 6 * 3 does not
+constexpr int kCsaPlanes = 5;         // weights 1 .. 16: the planes hold a count below kCsaGroup * kHomChunk = 32
+struct HomCsa {
+    uint32_t s[kCsaPlanes][2];
+    uint32_t f[2][2];
+    uint32_t cnt[kHomDigits];
+    uint32_t terms;
+    uint32_t pend;                           // carry words the fields may hold: groups, and add()'s blocks of 32 terms begun
+    uint32_t pend1;                          // add()'s terms in its current block of 32
+    uint32_t open[kCsaGroup][2], phase;      // add_chunk's carry words of a group that is not full yet
+    MIH_HD void init()
+    {
+        for (int v = 0; v < kCsaPlanes; ++v) s[v][0] = s[v][1] = 0;
+        for (int c = 0; c < 2; ++c) f[c][0] = f[c][1] = 0;
+        for (int t = 0; t < kHomDigits; ++t) cnt[t] = 0;
+        for (int c = 0; c < kCsaGroup; ++c) open[c][0] = open[c][1] = 0;
+        terms = 0; pend = 0; pend1 = 0; phase = 0;
+    }
+    // full adder on words: a + b + c = lo + 2 hi in every bit position (lo may be one of the inputs)
+    static MIH_HD void csa(uint32_t &hi, uint32_t &lo, uint32_t a, uint32_t b, uint32_t c)
+    {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && __has_builtin(__builtin_amdgcn_bitop3_b32)
+        // (two three-input bit operations, by truth table: the majority 0xE8 and the parity 0x96.  Left to itself the compiler
+        // regroups the adders of chunk_carry() into four to five two- and three-input operations each.)
+        const uint32_t m = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
+        lo = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+        hi = m;
+#else
+        const uint32_t t = a ^ b;
+        hi = (t & c) | (~t & a);
+        lo = t ^ c;
+#endif
+    }
+    // a chunk's 8 words into the planes of weight 1, 2, 4; c8: the carry word of weight 8 of either half.  Counts no terms.
+    MIH_HD void chunk_carry(const uint64_t (&U)[8], uint32_t (&c8)[2])
+    {
+        static_assert(kHomChunk == 8, "seven adders reduce eight words");
+        for (int w = 0; w < 2; ++w) {
+            uint32_t x[8], a2, b2, c2, d2, a4, b4;
+            for (int i = 0; i < 8; ++i) x[i] = (uint32_t)(U[i] >> (32 * w));
+            csa(a2, s[0][w], s[0][w], x[0], x[1]);
+            csa(b2, s[0][w], s[0][w], x[2], x[3]);
+            csa(a4, s[1][w], s[1][w], a2, b2);
+            csa(c2, s[0][w], s[0][w], x[4], x[5]);
+            csa(d2, s[0][w], s[0][w], x[6], x[7]);
+            csa(b4, s[1][w], s[1][w], c2, d2);
+            csa(c8[w], s[2][w], s[2][w], a4, b4);
+        }
+    }
+    // two carry words of weight 8 (zero where the list has no chunk any more) into the plane of weight 8; c16: the carry of weight 16
+    MIH_HD void pair_carry(const uint32_t (&a8)[2], const uint32_t (&b8)[2], uint32_t (&c16)[2])
+    {
+        for (int w = 0; w < 2; ++w) csa(c16[w], s[3][w], s[3][w], a8[w], b8[w]);
+    }
+    // a carry word of weight 32 into the 4-bit fields (the caller has made room: room_for_carry())
+    MIH_HD void add_carry32(int w, uint32_t c32)
+    {
+        for (int c = 0; c < 2; ++c) f[c][w] += (c32 >> (2 * c)) & 0x33333333u;
+    }
+    MIH_HD void room_for_carry()
+    {
+        if (pend == (uint32_t)kCsaFlush) flush();
+        ++pend;
+    }
+    // a group's two carry words of weight 16 into the plane of weight 16 and the fields; flushes at its own cadence.
+    // k_xtv_hom's call: once per round of kCsaGroup chunks, by the whole wave.
+    MIH_HD void add_pairs(const uint32_t (&a16)[2], const uint32_t (&b16)[2])
+    {
+        static_assert(kCsaGroup == 4 && kCsaPlanes == 5, "three adders reduce four carry words of weight 8 to one of weight 32");
+        room_for_carry();
+        for (int w = 0; w < 2; ++w) {
+            uint32_t c32;
+            csa(c32, s[4][w], s[4][w], a16[w], b16[w]);
+            add_carry32(w, c32);
+        }
+    }
+    // the carry words of a group's chunks
+    MIH_HD void add_group(const uint32_t (&c8)[kCsaGroup][2])
+    {
+        uint32_t a16[2], b16[2];
+        pair_carry(c8[0], c8[1], a16);
+        pair_carry(c8[2], c8[3], b16);
+        add_pairs(a16, b16);
+    }
+    MIH_HD void flush()
+    {
+        for (int w = 0; w < 2; ++w)
+            for (int c = 0; c < 2; ++c) {
+                for (int j = 0; j < 8; ++j) {
+                    const int t = 16 * w + 2 * j + c;
+                    if (t < kHomDigits) cnt[t] += ((f[c][w] >> (4 * j)) & 0xFu) << kCsaPlanes;
+                }
+                f[c][w] = 0;
+            }
+        pend = 0; pend1 = 0;
+    }
+    // a list's chunk of kHomChunk terms; the group closes with its kCsaGroup-th chunk (or in finish())
+    MIH_HD void add_chunk(const uint64_t (&U)[8])
+    {
+        chunk_carry(U, open[phase]);
+        terms += kHomChunk;
+        if (++phase == (uint32_t)kCsaGroup) close_group();
+    }
+    MIH_HD void close_group()
+    {
+        add_group(open);
+        for (int c = 0; c < kCsaGroup; ++c) open[c][0] = open[c][1] = 0;
+        phase = 0;
+    }
+    // one term: a half-adder chain through the planes.  A bit position sends a carry of weight 32 once in 32 terms, but the
+    // positions do so at different terms: a block of 32 terms counts as one carry word from its first term on (T terms since a
+    // flush() have sent a position at most ceil(T / 32) carries, its plane count being below 32 at the flush).
+    MIH_HD void add(uint64_t U)
+    {
+        if (pend1 == 0) room_for_carry();
+        if (++pend1 == (uint32_t)(kCsaGroup * kHomChunk)) pend1 = 0;
+        for (int w = 0; w < 2; ++w) {
+            uint32_t c = (uint32_t)(U >> (32 * w));
+            for (int v = 0; v < kCsaPlanes; ++v) { const uint32_t t = s[v][w] & c; s[v][w] ^= c; c = t; }
+            add_carry32(w, c);
+        }
+        ++terms;
+    }
+    // closes an open group with zero words and empties the fields and the planes into cnt[]: digit_sum() is exact from here on
+    // (more terms may follow)
+    MIH_HD void finish()
+    {
+        if (phase != 0) close_group();
+        flush();
+        for (int w = 0; w < 2; ++w)
+            for (int j = 0; j < 4; ++j) {
+                uint32_t b = 0;
+                for (int v = 0; v < kCsaPlanes; ++v) b += ((s[v][w] >> (2 * j)) & 0x03030303u) << v;
+                for (int i = 0; i < 4; ++i) {
+                    const int t = 16 * w + 4 * i + j;
+                    if (t < kHomDigits) cnt[t] += (b >> (8 * i)) & 0xFFu;
+                }
+            }
+        for (int v = 0; v < kCsaPlanes; ++v) s[v][0] = s[v][1] = 0;
+    }
+    MIH_HD int32_t digit_sum(int t) const { return (int32_t)cnt[t] - 2 * (int32_t)terms; }      // after finish()
+};
+
 // Where the 16-byte chunks of a slot group's lists live.  A slot group is the 64 consecutive slots one wave of k_xtv_hom owns; per
 // (slice, group, sub-slice) its lists share one block of sum cnt[] chunks, chunk-index-major and compacted: chunk 0 of every
 // lane that has one, in lane order, then chunk 1 of every lane that has two, ...  A wave's load of its chunks c is then one

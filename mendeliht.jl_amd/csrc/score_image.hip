@@ -194,10 +194,11 @@ k_img_lists(const uint4 *__restrict__ X, int64_t nbp, int splits, int nss, int64
 // E[slice][class-1 position][t] = sum of digit t of R over the position's dosage-2 rows in the slice.  A workgroup takes 512
 // positions of one row slice and walks the slice's sub-slices: U of the sub-slice's rows goes to LDS once, every thread then
 // follows its own list (16 B = 8 row numbers a load; the loads of a wave are one contiguous run of the group's block, and the
-// next one is in flight while this one is added) and adds up the 2-bit fields of U[row] in SWAR form (HomSum).  Integer sums:
-// no order to keep.  Runs between k_digits and the pass, under the same gate.
+// next one is in flight while this one is added) and counts the set bits of U[row] by position with carry-save adders, four
+// chunks a round (HomCsa of score_image.h; the digit sums are HomSum's).  Integer sums: no order to keep.  Runs between k_digits
+// and the pass, under the same gate.
 constexpr int kHomThreads = 512;
-__global__ void __launch_bounds__(kHomThreads)
+__global__ void __launch_bounds__(kHomThreads, 4)      // (4 waves a SIMD = two workgroups a CU: at most 128 VGPRs)
 k_xtv_hom(const unsigned long long *__restrict__ U, int64_t nbp, int splits, int nss, int64_t pos1, const uint32_t *__restrict__ seg_off,
           const uint16_t *__restrict__ rows, const int32_t *__restrict__ order, float *__restrict__ E, const int32_t *__restrict__ gate,
           int32_t gate_val)
@@ -212,8 +213,8 @@ k_xtv_hom(const unsigned long long *__restrict__ U, int64_t nbp, int splits, int
     const int64_t pos = slot < pos1 ? order[slot] : pos1;
     const int64_t bps = (nbp + splits - 1) / splits;
     const int64_t s0 = split * bps, s1 = std::min<int64_t>(s0 + bps, nbp);
-    HomSum hs;
-    hs.init();
+    HomCsa hc;
+    hc.init();
     if (threadIdx.x == 0) su[SUB] = hom_u(0);
     // The wave is one slot group (kHomGroup = 64 = the wave; pos1 is a multiple of 64, so a wave is live or not as a whole).  Its
     // offsets of a sub-slice are 64 consecutive entries of seg_off: a lane's chunk count is the difference to its successor's
@@ -266,34 +267,48 @@ k_xtv_hom(const unsigned long long *__restrict__ U, int64_t nbp, int splits, int
             uint64_t m = __ballot(cnt > 0u);
             uint4 v = make_uint4(0, 0, 0, 0);
             if (cnt > 0u) v = all[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))];
-            for (uint32_t c = 0; m != 0; ++c) {           // (wave-uniform: as many rounds as the longest list has chunks)
-                base += (uint32_t)__popcll(m);
-                const uint64_t m1 = __ballot(cnt > c + 1u);
-                uint4 vn = v;                             // chunk c + 1 is on its way while chunk c is gathered and added
-                if (cnt > c + 1u) vn = all[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u))];
-                if (cnt > c) {
-                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                    uint64_t u8[kHomChunk];
+            // (wave-uniform: rounds of kCsaGroup chunks, as many as the longest list needs; a list that has ended adds zero carry words)
+            for (uint32_t c = 0; m != 0; c += (uint32_t)kCsaGroup) {
+                uint32_t c16[kCsaGroup / 2][2];
+                #pragma unroll
+                for (int j2 = 0; j2 < kCsaGroup / 2; ++j2) {
+                    uint32_t c8[2][2];
                     #pragma unroll
-                    for (int i = 0; i < kHomChunk; ++i) u8[i] = su[(w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu];
-                    hs.add_chunk(u8);                                          // (folds and flushes at its own cadence, score_image.h)
+                    for (int j1 = 0; j1 < 2; ++j1) {
+                        const uint32_t cj = c + 2 * j2 + j1;
+                        base += (uint32_t)__popcll(m);
+                        const uint64_t m1 = __ballot(cnt > cj + 1u);
+                        uint4 vn = v;                     // chunk cj + 1 is on its way while chunk cj is gathered and added
+                        if (cnt > cj + 1u) vn = all[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u))];
+                        c8[j1][0] = c8[j1][1] = 0u;
+                        if (cnt > cj) {
+                            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                            uint64_t u8[kHomChunk];
+                            #pragma unroll
+                            for (int i = 0; i < kHomChunk; ++i) u8[i] = su[(w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu];
+                            hc.chunk_carry(u8, c8[j1]);                        // (seven adders a half, score_image.h)
+                        }
+                        v = vn;
+                        m = m1;
+                    }
+                    hc.pair_carry(c8[0], c8[1], c16[j2]);
                 }
-                v = vn;
-                m = m1;
+                hc.add_pairs(c16[0], c16[1]);                                  // (by the whole wave: its flush is one branch for all lanes)
             }
+            hc.terms += (uint32_t)kHomChunk * cnt;                            // (padding entries are terms, a missing chunk is not)
         }
         o_cur = o_nxt;
     }
     if (pos >= pos1) return;
-    hs.flush();
+    hc.finish();
     float *e = E + ((int64_t)split * pos1 + pos) * 32;
     #pragma unroll
     for (int q = 0; q < 8; ++q) {
         float4 f;
-        f.x = 4 * q + 0 < kHomDigits ? (float)hs.digit_sum(4 * q + 0 < kHomDigits ? 4 * q + 0 : 0) : 0.f;
-        f.y = 4 * q + 1 < kHomDigits ? (float)hs.digit_sum(4 * q + 1 < kHomDigits ? 4 * q + 1 : 0) : 0.f;
-        f.z = 4 * q + 2 < kHomDigits ? (float)hs.digit_sum(4 * q + 2 < kHomDigits ? 4 * q + 2 : 0) : 0.f;
-        f.w = 4 * q + 3 < kHomDigits ? (float)hs.digit_sum(4 * q + 3 < kHomDigits ? 4 * q + 3 : 0) : 0.f;
+        f.x = 4 * q + 0 < kHomDigits ? (float)hc.digit_sum(4 * q + 0 < kHomDigits ? 4 * q + 0 : 0) : 0.f;
+        f.y = 4 * q + 1 < kHomDigits ? (float)hc.digit_sum(4 * q + 1 < kHomDigits ? 4 * q + 1 : 0) : 0.f;
+        f.z = 4 * q + 2 < kHomDigits ? (float)hc.digit_sum(4 * q + 2 < kHomDigits ? 4 * q + 2 : 0) : 0.f;
+        f.w = 4 * q + 3 < kHomDigits ? (float)hc.digit_sum(4 * q + 3 < kHomDigits ? 4 * q + 3 : 0) : 0.f;
         reinterpret_cast<float4 *>(e)[q] = f;
     }
 }
