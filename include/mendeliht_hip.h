@@ -433,6 +433,62 @@ int mih_assoc_score_firth(const mih_mat *h, const double *A /* n: y - mu */, con
                           uint8_t *firth_state /* p */, int32_t *firth_evals /* p, may be NULL; 0 where not tried */,
                           double *neglog10p_spa /* p, may be NULL: no saddlepoint pass */, uint8_t *spa_state /* p */,
                           double *t_hat /* p x 2, may be NULL */);
+/* Gene-based burden and SKAT tests of sets of columns on top of the marginal scan, one trait, every handle kind (csrc/assoc_sets.hip;
+ * tests/sets_spec.py states the same in numpy).
+ * Inputs: A (n), w (n or NULL: ones), Z (n x c) and slice_rows exactly as mih_assoc_score takes them with t = 1.  nsets sets in CSR
+ * form: set_ptr (nsets + 1, starting at 0, non-decreasing), set_col (0-based column indices) and omega (one variant weight per
+ * entry, finite, >= 0).  Within a set the columns are strictly ascending and there are at most 128 of them; sets may overlap.
+ * The scan: U_j, b_j, Q_j, V_j, z_j, the degenerate rule, G = L L' and u_j = L^-1 b_j are mih_assoc_score's, computed by the same
+ * code; z, beta, se and neglog10p (p each) are its outputs bit for bit.
+ * Members of a set: its entries whose column is not degenerate and whose omega > 0, in entry order; m_used is their count m.
+ * Per set, over the members:
+ *   C_jk = sum_i w_i x~_ij x~_ik (j > k), x~ as mih_xtv multiplies it (the handle's centre, scale and impute flags, a missing entry
+ *          as the flags say) -- ONE chain of fused multiply-adds over the rows in ascending order, x~_ij w_i rounded first
+ *   K_jk = C_jk - sum_l u_jl u_kl (l ascending from 0.0, every operation rounded by itself);  K_jj = V_j, the scan's own value;
+ *          K mirrored to a full symmetric matrix
+ *   M_jk = (omega_j K_jk) omega_k for j >= k, mirrored
+ * Burden: a_j = omega_j U_j;  T = sum_j a_j;  rs_j = sum_k M_jk (k ascending), S = sum_j rs_j (j ascending);
+ *   burden_z = T / sqrt(S), NaN where S <= 0;  neglog10p_burden its two-sided normal tail (normal_tail.h).
+ * SKAT: skat_q = Q = sum_j a_j a_j;  lambda = the eigenvalues of M in descending order, every lambda_i <= 0 set to 0 (Jacobi on the
+ *   device, not bit-identical to another solver: within |M|_F m 2^-52 of the exact ones);  the p-value is P(sum lambda_i chi2_1 > Q) by
+ *   the saddlepoint approximation of Kuonen (1999):  K(t) = -1/2 sum log1p(-2 lambda_i t),  K' = sum lambda_i / (1 - 2 lambda_i t),
+ *   K'' = 2 sum (lambda_i / (1 - 2 lambda_i t))^2,  t_hat solves K'(t_hat) = Q on t < 1 / (2 lambda_1),
+ *   w = sign(t_hat) sqrt(2 (t_hat Q - K(t_hat))),  v = t_hat sqrt(K''(t_hat)),  r = w + log(v / w) / w,  the tail log Phi(-r).
+ *   The root iteration, in units of 1 / (2 lambda_1) (s = 2 lambda_1 t, mu_i = lambda_i / lambda_1, q = Q / lambda_1,
+ *   g(s) = sum mu_i / (1 - mu_i s), g2(s) = sum (mu_i / (1 - mu_i s))^2, w^2 = s q + sum log1p(-mu_i s), v = s sqrt(g2 / 2)):
+ *   s = 0, lo missing, hi = 1 (the pole).  Repeat: evaluate g, g2 (one evaluation), f = g - q;  |f| <= 2^-40 q: converged,
+ *   s_hat = s - f / g2 (one more Newton step), stop;  128 evaluations made: not converged, stop;  f < 0: lo = s, else hi = s;
+ *   sn = s - f / g2;  if not lo < sn < hi:  f < 0: sn = (s + hi) / 2;  f > 0: sn = (lo + s) / 2 if lo exists, else 2 s if s < 0, else -1;
+ *   s = sn.
+ * skat_state, decided in this order, and neglog10p_skat:
+ *   0  m = 0, or lambda_1 is not > 0 and finite: NaN
+ *   2  rank one, m = 1 or lambda_2 <= 2^-40 lambda_1: the exact chi2_1 tail of Q / lambda_1, as the two-sided normal tail of
+ *      sqrt(Q) / sqrt(lambda_1) -- a one-variant set with omega = 1 reproduces the scan's neglog10p bit for bit
+ *   4  Q <= 0: 0
+ *   5  the root iteration did not converge in 128 evaluations: the one-sided tail of the moment-matched normal
+ *      z = (Q - sum lambda) / sqrt(2 sum lambda^2)
+ *   3  near the mean, w^2 < 2^-40: the limit of r as w -> 0, r = kappa_3 / 6, kappa_3 = 8 sum lambda^3 / (2 sum lambda^2)^(3/2)
+ *   1  the saddlepoint tail
+ * A set without members has skat_q = 0 and NaN in burden_z and both p-values.
+ * lambda (may be NULL) is laid out like set_col: the lambda of a set first, NaN after m_used.  cov (may be NULL): sum m_s^2 doubles,
+ * m_s the entry count of set s (non-members included), each set's K over its entries in entry order, row-major, NaN in the rows
+ * and columns of non-members.
+ * Every set output is bit for bit independent of slice_rows, of the position of the set in the list and of the other sets.
+ * Memory: everything the call allocates -- the scan's buffers, per set its K (m_s^2 doubles) and, for a set of more than 64
+ * entries, a Jacobi slab ((m_s + 1)^2), the lists, u and the results -- is summed and compared with the free device memory before
+ * anything is allocated; MIH_OOM names both counts.  Everything is released before the call returns; the handle is only read.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: everything mih_assoc_score refuses at t = 1, a null m_used,
+ * burden_z, neglog10p_burden, skat_q, neglog10p_skat or skat_state, nsets < 0, a null set_ptr, a set_ptr that does not start at 0 or
+ * decreases, a set of more than 128 entries, null set_col or omega with entries, a column outside [0, p), columns of a set not
+ * strictly ascending, an omega that is negative or not finite.  nsets = 0 is valid and returns the scan alone.
+ * Not offered: SKAT-O, ACAT, saddlepoint-adjusted variances for unbalanced case-control sets, collapsing of ultra-rare variants,
+ * sets of more than 128 entries. */
+int mih_assoc_sets(const mih_mat *h, const double *A /* n */, const double *w /* n, or NULL */, const double *Z /* n x c */, int32_t c,
+                   int64_t slice_rows, int32_t nsets, const int64_t *set_ptr /* nsets + 1 */, const int32_t *set_col, const double *omega,
+                   double *z /* p */, double *beta /* p */, double *se /* p */, double *neglog10p /* p */,
+                   int32_t *m_used /* nsets */, double *burden_z /* nsets */, double *neglog10p_burden /* nsets */,
+                   double *skat_q /* nsets */, double *neglog10p_skat /* nsets */, uint8_t *skat_state /* nsets */,
+                   double *lambda /* like set_col, may be NULL */, double *cov /* sum m_s^2, may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

@@ -9,6 +9,7 @@ All numerics run in libmendeliht_hip.so on the GPU; this file only marshals.
 """
 import collections
 import ctypes as C
+import math
 import os
 import sys
 import time
@@ -186,6 +187,7 @@ def lib():
         "mih_assoc_score": [vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp],
         "mih_assoc_score_spa": [vp, vp, vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp],
         "mih_assoc_score_firth": [vp, vp, vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mih_assoc_sets": [vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mih_snp_naive_impute": [vp, vp],
         "mih_xtv": [vp, vp, vp],
         "mih_xtv_batched": [vp, vp, C.c_int, vp],
@@ -245,7 +247,7 @@ def exported_symbols():
             "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
             "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
             "mih_mat_score_image", "mih_device_trim",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_assoc_score", "mih_assoc_score_spa", "mih_assoc_score_firth", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
+            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_assoc_score", "mih_assoc_score_spa", "mih_assoc_score_firth", "mih_assoc_sets", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
             "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
             "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
             "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
@@ -565,6 +567,125 @@ class _Mat:
         null = fit_null(y, zc, d, l)
         res = self.score_test(null.A, null.w, zc, slice_rows)
         res.null = null
+        return res
+
+    def set_test(self, A, w, Z, sets, omega=None, slice_rows=0, cov=False):
+        """Burden and SKAT tests of sets of columns on top of the score test of every column -- mih_assoc_sets as it is: score
+        residuals A (n: one trait), working weights w (None: ones) and covariates Z (None: an intercept) as score_test takes
+        them.  sets: a list of index arrays (0-based columns, strictly ascending within a set, at most 128), or the pair
+        (set_ptr, set_col); omega: one weight >= 0 per entry, as a list of arrays like sets or one flat array (None: ones).
+        Returns a SetResult; cov=True also keeps every set's covariance K of the scores (a list of m_s x m_s arrays over the
+        entries, NaN in the rows and columns of entries that are not members)."""
+        from .assoc import AssocResult, SetResult
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.shape != (self.n,):
+            raise DimensionMismatch(f"A has shape {A.shape}, expected ({self.n},)")
+        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
+        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
+        if Z.ndim != 2 or Z.shape[0] != self.n:
+            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (self.n,):
+                raise DimensionMismatch(f"w has shape {w.shape}, expected ({self.n},)")
+        if isinstance(sets, tuple):                     # a tuple is (set_ptr, set_col), a list is a list of sets
+            if len(sets) != 2:
+                raise ArgumentError("sets as a tuple must be (set_ptr, set_col)")
+            ptr = np.ascontiguousarray(sets[0], dtype=np.int64)
+            col = np.ascontiguousarray(sets[1], dtype=np.int32)
+        else:
+            parts = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
+            ptr = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                ptr[1:] = np.cumsum([q.size for q in parts])
+            col = (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64))
+            if col.size and (col.min() < -2 ** 31 or col.max() >= 2 ** 31):
+                raise ArgumentError("a set names a column outside the int32 range")
+            col = np.ascontiguousarray(col, dtype=np.int32)
+        ns = ptr.size - 1
+        if ptr.ndim != 1 or col.ndim != 1 or ptr.size < 1 or int(ptr[-1]) != col.size:
+            raise ArgumentError(f"set_ptr must hold nsets + 1 offsets ending at the {col.size} entries of set_col")
+        if omega is None:
+            om = np.ones(col.size)
+        elif isinstance(omega, (list, tuple)) and len(omega) and np.ndim(omega[0]) >= 1:
+            om = np.concatenate([np.asarray(o, dtype=np.float64).reshape(-1) for o in omega])
+        else:
+            om = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+        om = np.ascontiguousarray(om, dtype=np.float64)
+        if om.size != col.size:
+            raise DimensionMismatch(f"omega has {om.size} entries, the sets have {col.size}")
+        z = np.empty(self.p); beta = np.empty(self.p); se = np.empty(self.p); nlp = np.empty(self.p)
+        k = max(ns, 0)
+        m_used = np.empty(k, dtype=np.int32); state = np.empty(k, dtype=np.uint8)
+        bz = np.empty(k); bn = np.empty(k); sq = np.empty(k); sn = np.empty(k)
+        lam = np.empty(col.size)
+        sizes = np.diff(ptr)
+        cv = np.empty(int((sizes * sizes).sum())) if cov else None
+        _check(lib().mih_assoc_sets(self._h, _p(A), _p(w), _p(Z), Z.shape[1], int(slice_rows), ns, _p(ptr), _p(col), _p(om),
+                                    _p(z), _p(beta), _p(se), _p(nlp), _p(m_used), _p(bz), _p(bn), _p(sq), _p(sn), _p(state), _p(lam), _p(cv)))
+        covs = None
+        if cov:
+            off = np.concatenate([[0], np.cumsum(sizes * sizes)]).astype(np.int64)
+            covs = [cv[off[s]:off[s + 1]].reshape(sizes[s], sizes[s]).copy() for s in range(ns)]
+        return SetResult(ptr, col, om, m_used, bz, bn, sq, sn, state, lam, covs, AssocResult(z, beta, se, nlp))
+
+    def assoc_sets(self, y, z, sets, *, d=None, l=None, weights="beta", beta=(1, 25), max_maf=None, slice_rows=0, cov=False):
+        """Gene-based burden and SKAT tests: the null model y ~ z (fit_null, as assoc fits it; z=None: an intercept; a Normal
+        trait is scaled by 1 / sqrt(phi) as in assoc) and set_test against it.  weights="beta": omega_j is the Beta(a, b) density
+        at the minor allele frequency of column j, beta = (a, b) -- SKAT's default (1, 25) -- divided by sinv_j on a scaled
+        handle.  The argument: on a scaled handle the column is x~_j = (g_j - mu_j) sinv_j; with an intercept in z the centring is
+        projected out, so U~_j = sinv_j U_j and K~_jk = sinv_j sinv_k K_jk for the raw genotypes' U and K, and omega_j / sinv_j
+        on the scaled column gives omega_j U_j and omega_j omega_k K_jk: SKAT's weighting of the raw genotypes, whatever the
+        flags of the handle.  weights may be an array of p weights instead (used as they are; a DenseMatrix, which has no allele
+        frequencies, takes only that).  max_maf: entries whose minor allele frequency is above it (or not a number) are dropped
+        from their sets.  Returns a SetResult whose `assoc.null` is the NullModel."""
+        from .assoc import fit_null
+        d = Normal() if d is None else _inst(d)
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1:
+            raise ArgumentError("assoc_sets takes one trait")
+        if y.shape[0] != self.n:
+            raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
+        zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
+        parts = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
+        for q in parts:
+            if q.size and (q.min() < 0 or q.max() >= self.p):
+                raise ArgumentError(f"a set names column {int(q.min() if q.min() < 0 else q.max())}, outside [0, {self.p})")
+        has_maf = hasattr(self, "_allele_maf")
+        maf = self._allele_maf() if has_maf else None
+        if isinstance(weights, str):
+            if weights != "beta":
+                raise ArgumentError(f"weights must be \"beta\" or an array of {self.p} weights, got {weights!r}")
+            if not has_maf:
+                raise ArgumentError("a DenseMatrix has no allele frequencies: give weights as an array")
+            a, b = float(beta[0]), float(beta[1])
+            with np.errstate(all="ignore"):
+                lg = math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b)
+                om = np.exp(lg + (a - 1.0) * np.log(maf) + (b - 1.0) * np.log1p(-maf))
+            if a == 1.0:
+                om = np.where(maf == 0.0, np.exp(lg), om)
+            scaled = isinstance(self, DosageMatrix) or bool(getattr(self, "scale", False))
+            if scaled:
+                om = om / self.mu_sigma()[1]
+            om = np.where(np.isfinite(om), om, 0.0)
+        else:
+            om = np.asarray(weights, dtype=np.float64)
+            if om.shape != (self.p,):
+                raise DimensionMismatch(f"weights has shape {om.shape}, expected ({self.p},)")
+        if max_maf is not None:
+            if not has_maf:
+                raise ArgumentError("a DenseMatrix has no allele frequencies: max_maf cannot be applied")
+            parts = [q[maf[q] <= float(max_maf)] for q in parts]
+        null = fit_null(y, zc, d, l)
+        if isinstance(d, Normal) and (l is None or _inst(l).code == 0):
+            A, w = (y - null.mu) / math.sqrt(null.phi), None
+        else:
+            A, w = null.A, null.w
+        res = self.set_test(A, w, zc, parts, [om[q] for q in parts], slice_rows=slice_rows, cov=cov)
+        if w is None:
+            rt = math.sqrt(null.phi)
+            res.assoc.beta, res.assoc.se = res.assoc.beta * rt, res.assoc.se * rt
+        res.assoc.null = null
         return res
 
     def xv_sparse(self, idx, val):
@@ -1962,6 +2083,48 @@ def gwas(plinkfile, d, *, phenotypes=6, covariates="", outfile="gwas.txt", exclu
                         + (f"\t{float(res.beta_firth[j])!r}\t{float(res.se_firth[j])!r}\t{float(res.neglog10p_firth[j])!r}\t{int(res.firth_state[j])}"
                            if firth else "") + "\n")
     return res
+
+
+def gwas_sets(plinkfile, d, setfile, *, phenotypes=6, covariates="", outfile="gwas_sets.txt", exclude_std_idx=(), device=0, l=None,
+              weights="beta", beta=(1, 25), max_maf=None, slice_rows=0):
+    """The gene-based tests of a file, beside gwas(): the inputs are parsed as gwas parses them; setfile has two
+    whitespace-separated columns `set_id snp_id` (lines starting with # are skipped), the SNP ids are those of the .bim; a set is
+    the SNPs of its id in .bim order, in the order the ids first appear.  An id the .bim does not have, and a set of more than
+    128 SNPs, are ArgumentErrors naming the first.  x.assoc_sets does the rest.  outfile: `set_id n_snps m_used burden_z
+    neglog10p_burden skat_q neglog10p_skat skat_state`, one row per set, tab-separated.  Returns (set ids, SetResult)."""
+    d = _inst(d)
+    x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, False, device, False)
+    if _is_multivariate(y):
+        raise ArgumentError("gwas_sets tests one phenotype at a time")
+    if l is None:
+        l = LogLink() if isinstance(d, NegativeBinomial) else canonicallink(d)
+    index = {}
+    for j, name in enumerate(info[2]):
+        index.setdefault(str(name), j)
+    members = {}
+    with open(setfile) as f:
+        for ln, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if len(tok) < 2:
+                raise ArgumentError(f"{setfile}, line {ln}: expected `set_id snp_id`")
+            if tok[1] not in index:
+                raise ArgumentError(f"{setfile}, line {ln}: SNP {tok[1]} of set {tok[0]} is not in {plinkfile}.bim")
+            members.setdefault(tok[0], set()).add(index[tok[1]])
+    ids = list(members)
+    sets = [np.array(sorted(members[k]), dtype=np.int64) for k in ids]
+    for k, s in zip(ids, sets):
+        if s.size > 128:
+            raise ArgumentError(f"set {k} has {s.size} SNPs, at most 128 are supported")
+    res = x.assoc_sets(y, z, sets, d=d, l=l, weights=weights, beta=beta, max_maf=max_maf, slice_rows=slice_rows)
+    if outfile:
+        with open(outfile, "w") as f:
+            f.write("set_id\tn_snps\tm_used\tburden_z\tneglog10p_burden\tskat_q\tneglog10p_skat\tskat_state\n")
+            for k, name in enumerate(ids):
+                f.write(f"{name}\t{int(res.set_ptr[k + 1] - res.set_ptr[k])}\t{int(res.m_used[k])}\t{float(res.burden_z[k])!r}\t"
+                        f"{float(res.neglog10p_burden[k])!r}\t{float(res.skat_q[k])!r}\t{float(res.neglog10p_skat[k])!r}\t{int(res.skat_state[k])}\n")
+    return ids, res
 
 
 def print_cv_results(io, errors, path, k):

@@ -173,3 +173,28 @@ class AssocResult:
 
     def __repr__(self):
         return f"AssocResult(p={self.z.shape[0]}, traits={1 if self.z.ndim == 1 else self.z.shape[1]})"
+
+
+class SetResult:
+    """The set-based tests of set_test / assoc_sets.  Per set: m_used (int32: the members -- entries whose column is not degenerate
+    and whose omega > 0), burden_z, neglog10p_burden, skat_q, neglog10p_skat and skat_state (uint8: 0 no value, 1 saddlepoint,
+    2 rank one: the exact chi-square tail, 3 at the mean: the limit, 4 Q <= 0: p = 1, 5 the root iteration gave up: the
+    moment-matched normal).  set_ptr, set_col, omega: the sets as they went in.  lambdas: the eigenvalues of every set's M, laid
+    out like set_col (NaN after m_used); lambdas_of(s) gives one set's.  cov: None, or the list of the sets' covariance matrices.
+    assoc: the AssocResult of the per-column scan of the same call."""
+    def __init__(self, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambdas, cov, assoc):
+        self.set_ptr, self.set_col, self.omega, self.m_used = set_ptr, set_col, omega, m_used
+        self.burden_z, self.neglog10p_burden, self.skat_q, self.neglog10p_skat = burden_z, neglog10p_burden, skat_q, neglog10p_skat
+        self.skat_state, self.lambdas, self.cov, self.assoc = skat_state, lambdas, cov, assoc
+
+    def lambdas_of(self, s):
+        return self.lambdas[self.set_ptr[s]:self.set_ptr[s] + self.m_used[s]]
+
+    def top(self, k, by="skat"):
+        """The k sets with the largest neglog10p_skat (by="burden": neglog10p_burden), falling; ties by index; sets without a value never."""
+        a = np.asarray(self.neglog10p_burden if by == "burden" else self.neglog10p_skat)
+        ok = np.flatnonzero(~np.isnan(a))
+        return ok[np.lexsort((ok, -a[ok]))][:int(k)]
+
+    def __repr__(self):
+        return f"SetResult(sets={self.m_used.shape[0]}, p={self.assoc.z.shape[0]})"

@@ -11,6 +11,7 @@
 #include "grm.h"
 #include "normal_tail.h"
 #include "assoc_spa.h"
+#include "assoc_sets.h"
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -330,9 +331,9 @@ struct SpaCall { const double *eta; double cutoff; double *neglog10p_spa; uint8_
 // what mih_assoc_score_firth adds to a call (nullptr: no Firth pass); with a SpaCall beside it both passes run on one selection
 struct FirthCall { const double *eta; double cutoff; double *beta, *se, *neglog10p; uint8_t *state; int32_t *evals; };
 
-// the body of the three entry points
+// the body of the four entry points (sets: what mih_assoc_sets adds, nullptr: no set pass)
 static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
-                           double *z, double *beta, double *se, double *neglog10p, double *wsum, const SpaCall *spa, const FirthCall *firth = nullptr)
+                           double *z, double *beta, double *se, double *neglog10p, double *wsum, const SpaCall *spa, const FirthCall *firth = nullptr, const SetsCall *sets = nullptr)
 {
     const char *who = firth ? "mih_assoc_score_firth" : "mih_assoc_score_spa";
     // ---- refusals: nothing allocated, nothing written ----
@@ -360,6 +361,7 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
     if (!all_finite(A, (size_t)n * (size_t)t)) { set_error("mih_assoc_score: a score residual is not finite"); return MIH_BAD_ARG; }
     if (!all_finite(Z, (size_t)n * (size_t)c)) { set_error("mih_assoc_score: a covariate is not finite"); return MIH_BAD_ARG; }
     if (eta && !all_finite(eta, (size_t)n)) { set_error("%s: a linear predictor is not finite", who); return MIH_BAD_ARG; }
+    if (sets) MIH_TRY(assoc_sets_check(*sets, p));
     std::vector<double> Linv;
     if (!assoc_null_factor(Z, w, n, c, Linv)) { set_error("mih_assoc_score: Z'WZ is not positive definite"); return MIH_BAD_ARG; }
 
@@ -397,8 +399,15 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
     const double need_spa = spa ? assoc_spa_bytes(n, p, (int)c) : firth ? assoc_flag_bytes(n, p, (int)c) : 0.0;
     const double need_firth = firth ? assoc_firth_bytes(p) : 0.0;
     need += need_spa + need_firth;
+    double sets_resident = 0.0;
+    const double need_sets = sets ? assoc_sets_bytes(*sets, (int)c, &sets_resident) : 0.0;
     size_t free_b = 0, total_b = 0;
     MIH_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (sets && need + need_sets > (double)free_b) {
+        set_error("mih_assoc_sets: the scan needs %.0f bytes of device memory and the set pass %.0f more (%.0f of them the covariance and Jacobi slabs of %d sets, the rest their lists, u and results), %.0f bytes are free",
+                  need, need_sets, sets_resident, (int)sets->nsets, (double)free_b);
+        return MIH_OOM;
+    }
     if (firth && need > (double)free_b) {
         set_error("mih_assoc_score_firth: the scan needs %.0f bytes of device memory, the selection %.0f more (the linear predictor, the flagged columns' alpha%s, %lld slabs of %lld adjusted genotypes, held once) and the Firth pass %.0f more (the roots of up to %lld columns), %.0f bytes are free",
                   need - need_spa - need_firth, need_spa, spa ? " and saddlepoint tails" : "", (long long)std::min<int64_t>(p, kSpaSlabs), (long long)n, need_firth,
@@ -525,6 +534,8 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         if (spa) MIH_TRY(assoc_spa_run(h, s, (int)c, fl, S.p, V.p, Zd.p, hn.data(), spa_v, spa_s, spa_t));
         if (firth) MIH_TRY(assoc_firth_run(h, s, (int)c, fl, S.p, V.p, Zd.p, hb.data(), hs.data(), hn.data(), f_b, f_se, f_n, f_s, f_e));
     }
+    SetsOut so;
+    if (sets) MIH_TRY(assoc_sets_run(h, s, (int)c, S.p, V.p, Ld.p, wd.p, *sets, so));
     memcpy(z, hz.data(), sizeof(double) * hz.size());
     memcpy(beta, hb.data(), sizeof(double) * hb.size());
     memcpy(se, hs.data(), sizeof(double) * hs.size());
@@ -540,6 +551,17 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         memcpy(firth->neglog10p, f_n.data(), sizeof(double) * f_n.size());
         memcpy(firth->state, f_s.data(), f_s.size());
         if (firth->evals) memcpy(firth->evals, f_e.data(), sizeof(int32_t) * f_e.size());
+    }
+    if (sets && sets->nsets > 0) {
+        const size_t ns = (size_t)sets->nsets;
+        memcpy(sets->m_used, so.m_used.data(), sizeof(int32_t) * ns);
+        memcpy(sets->burden_z, so.burden_z.data(), sizeof(double) * ns);
+        memcpy(sets->neglog10p_burden, so.nlp_burden.data(), sizeof(double) * ns);
+        memcpy(sets->skat_q, so.skat_q.data(), sizeof(double) * ns);
+        memcpy(sets->neglog10p_skat, so.nlp_skat.data(), sizeof(double) * ns);
+        memcpy(sets->skat_state, so.state.data(), ns);
+        if (sets->lambda && !so.lambda.empty()) memcpy(sets->lambda, so.lambda.data(), sizeof(double) * so.lambda.size());
+        if (sets->cov && !so.cov.empty()) memcpy(sets->cov, so.cov.data(), sizeof(double) * so.cov.size());
     }
     if (wsum)
         for (int64_t j = 0; j < p; ++j)
@@ -575,6 +597,15 @@ int mih_assoc_score_firth(const mih_mat *h, const double *A, const double *w, co
     const FirthCall firth = {eta, cutoff, beta_firth, se_firth, neglog10p_firth, firth_state, firth_evals};
     const SpaCall spa = {eta, cutoff, neglog10p_spa, spa_state, t_hat};
     return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, neglog10p_spa ? &spa : nullptr, &firth);
+}
+
+int mih_assoc_sets(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, int64_t slice_rows, int32_t nsets,
+                   const int64_t *set_ptr, const int32_t *set_col, const double *omega, double *z, double *beta, double *se, double *neglog10p,
+                   int32_t *m_used, double *burden_z, double *neglog10p_burden, double *skat_q, double *neglog10p_skat, uint8_t *skat_state,
+                   double *lambda, double *cov)
+{
+    const SetsCall sets = {nsets, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambda, cov};
+    return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, nullptr, nullptr, &sets);
 }
 
 }  // extern "C"

@@ -13,6 +13,25 @@ struct SpaMat {
     const int64_t *miss_ptr; const int32_t *miss_row;
 };
 
+// The pieces of the per-kind column decode that every kernel working on decoded columns shares (the slabs below, the set Gram
+// of assoc_sets.hip).  2-bit: the four values of a column as k_xtv_finalize multiplies them (k_ib_solve's expressions) -- codes
+// 0, 1, 2 and a row of the column's missing list (the list holds a column's rows in ascending order, as the constructors write it).
+struct SnpVals { double x0, x1, x2, xm; };
+__device__ __forceinline__ SnpVals snp_vals(const SpaMat &m, int64_t j)
+{
+#pragma clang fp contract(off)
+    const double s = m.scale ? m.sinv[j] : 1.0, cm = m.center ? m.mu[j] : 0.0;
+    SnpVals v;
+    v.x0 = (0.0 - cm) * s; v.x1 = (1.0 - cm) * s; v.x2 = (2.0 - cm) * s; v.xm = ((m.impute ? m.mu[j] : 0.0) - cm) * s;
+    return v;
+}
+// dense f64 (KIND 0), dense f32 (1) and 16-bit dosage (2): the entry mih_xtv multiplies
+template <int KIND>
+__device__ __forceinline__ double slab_dense_x(const SpaMat &m, int64_t n, int64_t j, int64_t i)
+{
+    return KIND == 0 ? m.D[j * n + i] : KIND == 1 ? (double)m.Df[j * n + i] : dosage_x(m.dv, j, i);
+}
+
 // red[v][0] becomes the sum of red[v][0 .. 256), v < nv, over the fixed tree k = 128, 64, ... 1: red[tid] += red[tid + k]
 __device__ __forceinline__ void spa_tree(double (*red)[256], int nv)
 {
@@ -69,8 +88,8 @@ __device__ __forceinline__ void spa_slab_form(const SpaMat &m, int64_t n, int64_
 #pragma clang fp contract(off)
     const int tid = threadIdx.x;
     if (KIND == 3) {                                     // the stored codes first, then the column's missing rows over them
-        const double s = m.scale ? m.sinv[j] : 1.0, cm = m.center ? m.mu[j] : 0.0;
-        const double x0 = (0.0 - cm) * s, x1 = (1.0 - cm) * s, x2 = (2.0 - cm) * s, xm = ((m.impute ? m.mu[j] : 0.0) - cm) * s;
+        const SnpVals sv = snp_vals(m, j);
+        const double x0 = sv.x0, x1 = sv.x1, x2 = sv.x2, xm = sv.xm;
         for (int64_t i = tid; i < n; i += 256) {
             const uint32_t g = (m.X[xword(m.nbp, j, i >> 4)] >> (2 * (int)(i & 15))) & 3u;
             cs[i] = g == 0u ? x0 : g == 1u ? x1 : x2;
@@ -85,7 +104,7 @@ __device__ __forceinline__ void spa_slab_form(const SpaMat &m, int64_t n, int64_
     // c_i, M1 = sum c_i mu_i and the two ends of the range
     a0 = 0.0; a1 = 0.0; a2 = 0.0;
     for (int64_t i = tid; i < n; i += 256) {
-        const double x = KIND == 0 ? m.D[j * n + i] : KIND == 1 ? (double)m.Df[j * n + i] : KIND == 2 ? dosage_x(m.dv, j, i) : cs[i];
+        const double x = KIND == 3 ? cs[i] : slab_dense_x<KIND>(m, n, j, i);
         double za = 0.0;
         for (int k = 0; k < c; ++k) za = za + Z[(int64_t)k * n + i] * al[k];
         const double cc = x - za;
