@@ -123,6 +123,103 @@ PROFILE_COUNTERS = ("lanes", "max_in_flight", "handovers", "shared_init", "round
 
 _PROGRESS = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double)
 
+# The ctypes argument types of every function include/mendeliht_hip.h declares (all return int).  lib() applies them, and
+# exported_symbols() is this table's keys: tests/test_abi_cpu.py holds them against the header, so a declared function without a
+# signature fails there.
+_vp, _i64, _i32, _dbl = C.c_void_p, C.c_int64, C.c_int32, C.c_double
+_SIGNATURES = {
+    "mih_device_count": [C.POINTER(C.c_int)],
+    "mih_last_error": [C.c_char_p, C.c_size_t],
+    "mih_version": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "mih_snp_create": [_vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
+    "mih_snp_create_synthetic": [_i64, _i64, C.c_uint64, _dbl, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
+    "mih_snp_create_synthetic_shard": [_i64, _i64, _i64, C.c_uint64, _dbl, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
+    "mih_dense_create": [_vp, _i64, _i64, C.c_int, C.POINTER(_vp)],
+    "mih_dense_create_synthetic": [_i64, _i64, C.c_uint64, C.c_int, C.POINTER(_vp)],
+    "mih_dense_create_f32": [_vp, _i64, _i64, C.c_int, C.POINTER(_vp)],
+    "mih_dosage_create": [_vp, _i64, _i64, _i64, _i32, C.c_int, C.POINTER(_vp)],
+    "mih_dosage_create_synthetic": [_i64, _i64, C.c_uint64, _i32, _dbl, C.c_int, C.POINTER(_vp)],
+    "mih_dosage_export": [_vp, _i64, _i64, _vp],
+    "mih_dosage_create_bgen": [C.c_char_p, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64),
+                               C.POINTER(_i32)],
+    "mih_vcf_open": [C.c_char_p, C.c_int, _i64, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i32)],
+    "mih_vcf_info": [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64)],
+    "mih_vcf_header": [_vp, C.c_char_p, _i64, C.POINTER(_i64)],
+    "mih_dosage_create_vcf": [_vp, C.c_int, _i64, _i64, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)],
+    "mih_vcf_meta": [_vp, C.c_char_p, _i64, C.POINTER(_i64)],
+    "mih_vcf_inflate": [_vp, C.c_int, C.POINTER(_i64)],
+    "mih_vcf_close": [_vp],
+    "mih_dosage_regrid": [_vp, _i32],
+    "mih_snp_builder_create": [_i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
+    "mih_snp_builder_add": [_vp, _i64, _vp, C.POINTER(_i64)],
+    "mih_snp_builder_finish": [_vp, C.POINTER(_vp)],
+    "mih_snp_builder_destroy": [_vp],
+    "mih_snp_create_dosage": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(_i64)],
+    "mih_snp_create_vcf": [_vp, C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(_i64),
+                           C.POINTER(_i32)],
+    "mih_mat_destroy": [_vp],
+    "mih_mat_dims": [_vp, C.POINTER(_i64), C.POINTER(_i64)],
+    "mih_mat_reserve": [_vp, _i64],
+    "mih_mat_score_image": [_vp, C.c_int, _dbl, C.POINTER(_i64), C.POINTER(_i64)],
+    "mih_device_trim": [C.c_int, C.POINTER(_i64)],
+    "mih_snp_mu_sigma": [_vp, _vp, _vp],
+    "mih_snp_export_bed": [_vp, _vp],
+    "mih_snp_counts": [_vp, _vp, _vp, _vp, _vp],
+    "mih_snp_subset": [_vp, _vp, _i64, _vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
+    "mih_grm": [_vp, _vp, C.c_int, _i64, _vp],
+    "mih_grm_pairs": [_vp, _vp, C.c_int, _i64, _dbl, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp],
+    "mih_grm_eig": [_vp, _vp, C.c_int, _i64, _i32, _i32, _dbl, _i32, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)],
+    "mih_ld_band": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
+    "mih_ld_pairs": [_vp, _i64, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64)],
+    "mih_ld_prune": [_vp, _i64, _i64, _dbl, _i64, _i64, _vp, C.POINTER(_i64)],
+    "mih_assoc_score": [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
+    "mih_assoc_score_spa": [_vp, _vp, _vp, _vp, _i32, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mih_assoc_score_firth": [_vp, _vp, _vp, _vp, _i32, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mih_assoc_sets": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mih_snp_naive_impute": [_vp, _vp],
+    "mih_xtv": [_vp, _vp, _vp],
+    "mih_xtv_batched": [_vp, _vp, C.c_int, _vp],
+    "mih_xtv_batched_fmt": [_vp, _vp, C.c_int, C.c_int, _vp],
+    "mih_xv_sparse": [_vp, _vp, _vp, _i64, _vp],
+    "mih_project_topk": [_vp, _i64, _i64, C.POINTER(_i64)],
+    "mih_project_group_sparse": [_vp, _vp, _i64, _i64, _vp, C.c_int],
+    "mih_fit_iht": [_vp, C.POINTER(_FitParams), _vp, _vp, _i64, _vp, C.POINTER(_FitResult)],
+    "mih_cv_iht": [_vp, C.POINTER(_FitParams), _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _i32, _vp],
+    "mih_cv_meanloss": [_vp, _vp, _i64, _i32, _i64, _vp],
+    "mih_cv_assignment": [_vp, _i64, _i32, _i32, _vp],
+    "mih_fit_iht_path": [_vp, C.POINTER(_FitParams), _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp],
+    "mih_cv_iht_multi": [_vp, _i32, C.POINTER(_FitParams), _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp],
+    "mih_fit_mv": [_vp, C.POINTER(_FitParams), _vp, _i64, _vp, _i64, _vp, C.POINTER(_MvResult)],
+    "mih_cv_mv": [_vp, C.POINTER(_FitParams), _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _i32, _vp],
+    "mih_bench_xtv": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_float), C.POINTER(_dbl)],
+    "mih_xtv_algorithmic_bytes": [_vp, C.c_int, C.POINTER(_dbl)],
+    "mih_abi_sizes": [_vp, _i32],
+    "mih_session_create": [_vp, C.POINTER(_FitParams), _vp, _vp, _i64, _vp, C.POINTER(_vp)],
+    "mih_session_step": [_vp, C.POINTER(_dbl), C.POINTER(_i32), C.POINTER(_dbl)],
+    "mih_session_run": [_vp, _i64, C.POINTER(_dbl), C.POINTER(_i64), C.POINTER(_dbl)],
+    "mih_session_model": [_vp, _vp, _vp],
+    "mih_session_destroy": [_vp],
+    "mih_rccl_unique_id": [_vp],
+    "mih_comm_create_rccl": [_vp, _i32, _i32, _i32, _i64, _i64, C.POINTER(_vp)],
+    "mih_comm_destroy_rccl": [_vp],
+    "mih_comm_info": [_vp, C.POINTER(_i32), _vp, _i64],
+    "mih_cv_allgather": [_vp, _vp, _i64],
+    "mih_profile_enable": [_vp, C.c_int],
+    "mih_profile_read": [_vp, C.POINTER(_dbl), C.POINTER(_i64), C.c_int],
+    "mih_profile_passes": [_vp, C.POINTER(_PassRecord), _i64, C.POINTER(_i64), C.c_int],
+    "mih_profile_counters": [_vp, C.POINTER(_i64), C.c_int],
+    "mih_profile_exchange": [_vp, C.POINTER(_dbl), C.POINTER(_i64), C.c_int],
+}
+# include/mendeliht_hip_probes.h: exported by the measurement build only
+_PROBE_SIGNATURES = {
+    "mih_probe_set_xtv_variant": [C.c_int], "mih_probe_set_xtv_multi_variant": [C.c_int],
+    "mih_probe_set_max_fused": [C.c_int],
+    "mih_probe_xtv_sequence": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "mih_probe_xv_sequence": [_vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mih_probe_debias_glm": [_vp, _vp, _i64, _vp, C.c_int, C.c_int, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "mih_probe_init_beta": [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+}
+
 _lib = None
 
 
@@ -138,97 +235,9 @@ def lib():
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for this path.")
     L = C.CDLL(path)
-    vp, i64, i32, dbl = C.c_void_p, C.c_int64, C.c_int32, C.c_double
-    sig = {
-        "mih_device_count": [C.POINTER(C.c_int)],
-        "mih_last_error": [C.c_char_p, C.c_size_t],
-        "mih_version": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
-        "mih_snp_create": [vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
-        "mih_snp_create_synthetic": [i64, i64, C.c_uint64, dbl, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
-        "mih_snp_create_synthetic_shard": [i64, i64, i64, C.c_uint64, dbl, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
-        "mih_dense_create": [vp, i64, i64, C.c_int, C.POINTER(vp)],
-        "mih_dense_create_synthetic": [i64, i64, C.c_uint64, C.c_int, C.POINTER(vp)],
-        "mih_dense_create_f32": [vp, i64, i64, C.c_int, C.POINTER(vp)],
-        "mih_dosage_create": [vp, i64, i64, i64, i32, C.c_int, C.POINTER(vp)],
-        "mih_dosage_create_synthetic": [i64, i64, C.c_uint64, i32, dbl, C.c_int, C.POINTER(vp)],
-        "mih_dosage_export": [vp, i64, i64, vp],
-        "mih_dosage_create_bgen": [C.c_char_p, i64, i64, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64),
-                                   C.POINTER(i32)],
-        "mih_vcf_open": [C.c_char_p, C.c_int, i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32)],
-        "mih_vcf_info": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)],
-        "mih_vcf_header": [vp, C.c_char_p, i64, C.POINTER(i64)],
-        "mih_dosage_create_vcf": [vp, C.c_int, i64, i64, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)],
-        "mih_vcf_meta": [vp, C.c_char_p, i64, C.POINTER(i64)],
-        "mih_vcf_inflate": [vp, C.c_int, C.POINTER(i64)],
-        "mih_vcf_close": [vp],
-        "mih_dosage_regrid": [vp, i32],
-        "mih_snp_builder_create": [i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
-        "mih_snp_builder_add": [vp, i64, vp, C.POINTER(i64)],
-        "mih_snp_builder_finish": [vp, C.POINTER(vp)],
-        "mih_snp_builder_destroy": [vp],
-        "mih_snp_create_dosage": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i64)],
-        "mih_snp_create_vcf": [vp, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i64),
-                               C.POINTER(i32)],
-        "mih_mat_destroy": [vp],
-        "mih_mat_dims": [vp, C.POINTER(i64), C.POINTER(i64)],
-        "mih_mat_reserve": [vp, i64],
-        "mih_mat_score_image": [vp, C.c_int, dbl, C.POINTER(i64), C.POINTER(i64)],
-        "mih_device_trim": [C.c_int, C.POINTER(i64)],
-        "mih_snp_mu_sigma": [vp, vp, vp],
-        "mih_snp_export_bed": [vp, vp],
-        "mih_snp_counts": [vp, vp, vp, vp, vp],
-        "mih_snp_subset": [vp, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
-        "mih_grm": [vp, vp, C.c_int, i64, vp],
-        "mih_grm_pairs": [vp, vp, C.c_int, i64, dbl, i64, vp, vp, vp, C.POINTER(i64), vp],
-        "mih_grm_eig": [vp, vp, C.c_int, i64, i32, i32, dbl, i32, C.c_uint64, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)],
-        "mih_ld_band": [vp, i64, i64, i64, vp, vp, vp],
-        "mih_ld_pairs": [vp, i64, dbl, i64, i64, i64, vp, vp, vp, C.POINTER(i64)],
-        "mih_ld_prune": [vp, i64, i64, dbl, i64, i64, vp, C.POINTER(i64)],
-        "mih_assoc_score": [vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp],
-        "mih_assoc_score_spa": [vp, vp, vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp],
-        "mih_assoc_score_firth": [vp, vp, vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "mih_assoc_sets": [vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "mih_snp_naive_impute": [vp, vp],
-        "mih_xtv": [vp, vp, vp],
-        "mih_xtv_batched": [vp, vp, C.c_int, vp],
-        "mih_xtv_batched_fmt": [vp, vp, C.c_int, C.c_int, vp],
-        "mih_xv_sparse": [vp, vp, vp, i64, vp],
-        "mih_project_topk": [vp, i64, i64, C.POINTER(i64)],
-        "mih_project_group_sparse": [vp, vp, i64, i64, vp, C.c_int],
-        "mih_fit_iht": [vp, C.POINTER(_FitParams), vp, vp, i64, vp, C.POINTER(_FitResult)],
-        "mih_cv_iht": [vp, C.POINTER(_FitParams), vp, vp, i64, vp, i32, vp, i64, i32, i32, vp],
-        "mih_cv_meanloss": [vp, vp, i64, i32, i64, vp],
-        "mih_cv_assignment": [vp, i64, i32, i32, vp],
-        "mih_fit_iht_path": [vp, C.POINTER(_FitParams), vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp],
-        "mih_cv_iht_multi": [vp, i32, C.POINTER(_FitParams), vp, vp, i64, vp, i32, vp, i64, vp],
-        "mih_fit_mv": [vp, C.POINTER(_FitParams), vp, i64, vp, i64, vp, C.POINTER(_MvResult)],
-        "mih_cv_mv": [vp, C.POINTER(_FitParams), vp, i64, vp, i64, vp, i32, vp, i64, i32, i32, vp],
-        "mih_bench_xtv": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_float), C.POINTER(dbl)],
-        "mih_xtv_algorithmic_bytes": [vp, C.c_int, C.POINTER(dbl)],
-        "mih_abi_sizes": [vp, i32],
-        "mih_session_create": [vp, C.POINTER(_FitParams), vp, vp, i64, vp, C.POINTER(vp)],
-        "mih_session_step": [vp, C.POINTER(dbl), C.POINTER(i32), C.POINTER(dbl)],
-        "mih_session_run": [vp, i64, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl)],
-        "mih_session_model": [vp, vp, vp],
-        "mih_session_destroy": [vp],
-        "mih_rccl_unique_id": [vp],
-        "mih_comm_create_rccl": [vp, i32, i32, i32, i64, i64, C.POINTER(vp)],
-        "mih_comm_destroy_rccl": [vp],
-        "mih_comm_info": [vp, C.POINTER(i32), vp, i64],
-        "mih_cv_allgather": [vp, vp, i64],
-        "mih_profile_enable": [vp, C.c_int],
-        "mih_profile_read": [vp, C.POINTER(dbl), C.POINTER(i64), C.c_int],
-        "mih_profile_passes": [vp, C.POINTER(_PassRecord), i64, C.POINTER(i64), C.c_int],
-        "mih_profile_counters": [vp, C.POINTER(i64), C.c_int],
-        "mih_profile_exchange": [vp, C.POINTER(dbl), C.POINTER(i64), C.c_int],
-    }
-    if using_probes():       # include/mendeliht_hip_probes.h
-        sig.update({"mih_probe_set_xtv_variant": [C.c_int], "mih_probe_set_xtv_multi_variant": [C.c_int],
-                    "mih_probe_set_max_fused": [C.c_int],
-                    "mih_probe_xtv_sequence": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
-                    "mih_probe_xv_sequence": [vp, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp],
-                    "mih_probe_debias_glm": [vp, vp, i64, vp, C.c_int, C.c_int, dbl, vp, vp, vp, vp, vp],
-                    "mih_probe_init_beta": [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]})
+    sig = dict(_SIGNATURES)
+    if using_probes():
+        sig.update(_PROBE_SIGNATURES)
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
@@ -239,26 +248,12 @@ def lib():
 
 def exported_symbols():
     """Every symbol include/mendeliht_hip.h declares (checked by the CPU test-suite)."""
-    return ["mih_device_count", "mih_last_error", "mih_version", "mih_snp_create", "mih_snp_create_synthetic",
-            "mih_snp_create_synthetic_shard",
-            "mih_dense_create", "mih_dense_create_synthetic", "mih_dense_create_f32",
-            "mih_dosage_create", "mih_dosage_create_synthetic", "mih_dosage_export",
-            "mih_dosage_create_bgen", "mih_vcf_open", "mih_vcf_info", "mih_vcf_header", "mih_dosage_create_vcf", "mih_vcf_meta",
-            "mih_vcf_inflate", "mih_vcf_close", "mih_dosage_regrid", "mih_snp_builder_create", "mih_snp_builder_add",
-            "mih_snp_builder_finish", "mih_snp_builder_destroy", "mih_snp_create_dosage", "mih_snp_create_vcf", "mih_mat_destroy", "mih_mat_dims", "mih_mat_reserve",
-            "mih_mat_score_image", "mih_device_trim",
-            "mih_snp_mu_sigma", "mih_snp_export_bed", "mih_snp_naive_impute", "mih_snp_counts", "mih_snp_subset", "mih_grm", "mih_grm_pairs", "mih_grm_eig", "mih_ld_band", "mih_ld_pairs", "mih_ld_prune", "mih_assoc_score", "mih_assoc_score_spa", "mih_assoc_score_firth", "mih_assoc_sets", "mih_xtv", "mih_xtv_batched", "mih_xv_sparse",
-            "mih_project_topk", "mih_project_group_sparse", "mih_fit_iht", "mih_cv_iht", "mih_cv_meanloss", "mih_cv_assignment", "mih_cv_iht_multi", "mih_fit_iht_path",
-            "mih_fit_mv", "mih_cv_mv", "mih_bench_xtv", "mih_xtv_algorithmic_bytes", "mih_xtv_batched_fmt", "mih_abi_sizes",
-            "mih_session_create", "mih_session_step", "mih_session_run", "mih_session_model", "mih_session_destroy",
-            "mih_rccl_unique_id", "mih_comm_create_rccl", "mih_comm_info", "mih_comm_destroy_rccl", "mih_cv_allgather",
-            "mih_profile_enable", "mih_profile_read", "mih_profile_passes", "mih_profile_counters", "mih_profile_exchange"]
+    return list(_SIGNATURES)
 
 
 def probe_symbols():
     """What include/mendeliht_hip_probes.h declares: exported by the measurement build only."""
-    return ["mih_probe_set_xtv_variant", "mih_probe_set_xtv_multi_variant", "mih_probe_set_max_fused", "mih_probe_xtv_sequence",
-            "mih_probe_xv_sequence", "mih_probe_debias_glm", "mih_probe_init_beta"]
+    return list(_PROBE_SIGNATURES)
 
 
 def _check(rc):
@@ -393,6 +388,62 @@ def read_bed(path, n):
     return np.memmap(path, dtype=np.uint8, mode="r", offset=3, shape=((size - 3) // stride, stride))
 
 
+def _scan_args(n, A, w, Z, eta=None, traits=False):
+    """The arrays of a score_test* / set_test call on a matrix of n rows, as ctypes takes them: (A, w, Z, eta), float64.
+    traits=True (score_test): A is n, or n x t, and goes in as n x t in Fortran order; a fifth value says whether it was 1-D.
+    Otherwise A is one contiguous trait (n,).  Z (None: an intercept; 1-D: reshaped to n rows) is n x c in Fortran order.  w is
+    (n,), or None for unit weights.  With eta (the saddlepoint and Firth calls) w and eta are both required, (n,): a None among
+    them is refused for its shape like any other.  A wrong shape is a DimensionMismatch that names the argument."""
+    def vec(name, v):
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (n,):
+            raise DimensionMismatch(f"{name} has shape {v.shape}, expected ({n},)")
+        return v
+    if traits:
+        A = np.asarray(A, dtype=np.float64)
+        one = A.ndim == 1
+        A = np.asfortranarray(A[:, None] if one else A)
+        if A.ndim != 2 or A.shape[0] != n:
+            raise DimensionMismatch(f"A has shape {A.shape}, expected {n} rows")
+    else:
+        A = vec("A", A)
+    if eta is not None:
+        w, eta = vec("w", w), vec("eta", eta)
+    Z = np.ones((n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
+    Z = np.asfortranarray(Z.reshape(n, -1) if Z.ndim == 1 else Z)
+    if Z.ndim != 2 or Z.shape[0] != n:
+        raise DimensionMismatch(f"Z has shape {Z.shape}, expected {n} rows")
+    if eta is None and w is not None:
+        w = vec("w", w)
+    return (A, w, Z, eta, one) if traits else (A, w, Z, eta)
+
+
+def _plain_out(p):
+    """z, beta, se and neglog10p of a one-trait scan, for the library to fill"""
+    return [np.empty(p) for _ in range(4)]
+
+
+def _spa_out(p, on=True):
+    """the saddlepoint outputs by their AssocResult names, in the order the library takes them (on=False: not asked for)"""
+    return {"neglog10p_spa": np.empty(p) if on else None, "spa_state": np.empty(p, dtype=np.uint8) if on else None,
+            "t_hat": np.empty((p, 2), order="F") if on else None}
+
+
+def _null_scores(y, zc, d, l):
+    """The null model of y ~ zc (fit_null) and what the score test takes of it: (null, A, w, rt).  A Normal trait with the
+    identity link goes in with unit weights (w None), scaled by 1 / sqrt(phi): z is exact this way, and beta and se take the
+    trait's rt = sqrt(phi) afterwards; null is then a list with one model per column of y, A is n x t and rt has t entries.
+    Otherwise rt is None."""
+    from .assoc import fit_null
+    if isinstance(d, Normal) and (l is None or _inst(l).code == 0):
+        cols = y.T if y.ndim == 2 else [y]
+        nulls = [fit_null(col, zc, d, l) for col in cols]
+        rt = np.sqrt(np.array([m.phi for m in nulls]))
+        return nulls, np.stack([(col - m.mu) / r for col, m, r in zip(cols, nulls, rt)], axis=1), None, rt
+    null = fit_null(y, zc, d, l)
+    return null, null.A, null.w, None
+
+
 class _Mat:
     def __init__(self):
         self._h = C.c_void_p(None)
@@ -441,19 +492,7 @@ class _Mat:
         (None: an intercept) -- mih_assoc_score as it is.  Returns an AssocResult; wsum=True also keeps the class-weight sums
         W1, W2, Wm (p x 3) of a 2-bit matrix."""
         from .assoc import AssocResult
-        A = np.asarray(A, dtype=np.float64)
-        one = A.ndim == 1
-        A = np.asfortranarray(A[:, None] if one else A)
-        if A.ndim != 2 or A.shape[0] != self.n:
-            raise DimensionMismatch(f"A has shape {A.shape}, expected {self.n} rows")
-        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
-        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
-        if Z.ndim != 2 or Z.shape[0] != self.n:
-            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64)
-            if w.shape != (self.n,):
-                raise DimensionMismatch(f"w has shape {w.shape}, expected ({self.n},)")
+        A, w, Z, _, one = _scan_args(self.n, A, w, Z, traits=True)
         t, c = A.shape[1], Z.shape[1]
         z = np.empty((self.p, t), order="F"); beta = np.empty((self.p, t), order="F"); nlp = np.empty((self.p, t), order="F")
         se = np.empty(self.p)
@@ -469,22 +508,12 @@ class _Mat:
         intercept); columns with |z| >= cutoff are tried (inf: none).  Returns an AssocResult with neglog10p_spa, spa_state
         (0 not tried, 1 saddlepoint, 2 refused: the normal value) and t_hat (p x 2)."""
         from .assoc import AssocResult
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        eta = np.ascontiguousarray(eta, dtype=np.float64)
-        for name, v in (("A", A), ("w", w), ("eta", eta)):
-            if v.shape != (self.n,):
-                raise DimensionMismatch(f"{name} has shape {v.shape}, expected ({self.n},)")
-        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
-        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
-        if Z.ndim != 2 or Z.shape[0] != self.n:
-            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
-        z = np.empty(self.p); beta = np.empty(self.p); se = np.empty(self.p); nlp = np.empty(self.p); spa = np.empty(self.p)
-        state = np.empty(self.p, dtype=np.uint8)
-        that = np.empty((self.p, 2), order="F")
+        A, w, Z, eta = _scan_args(self.n, A, w, Z, eta=np.asarray(eta, dtype=np.float64))
+        z, beta, se, nlp = _plain_out(self.p)
+        sp = _spa_out(self.p)
         _check(lib().mih_assoc_score_spa(self._h, _p(A), _p(w), _p(Z), Z.shape[1], _p(eta), float(cutoff), int(slice_rows),
-                                         _p(z), _p(beta), _p(se), _p(nlp), _p(spa), _p(state), _p(that)))
-        return AssocResult(z, beta, se, nlp, neglog10p_spa=spa, spa_state=state, t_hat=that)
+                                         _p(z), _p(beta), _p(se), _p(nlp), *map(_p, sp.values())))
+        return AssocResult(z, beta, se, nlp, **sp)
 
     def score_test_firth(self, A, w, Z, eta, cutoff=2.0, slice_rows=0, spa=False):
         """The score test of every column for one Bernoulli trait with the logit link, with the Firth-penalised effect size and
@@ -493,28 +522,16 @@ class _Mat:
         1 penalised-likelihood values, 2 refused: the plain values) and firth_evals; spa=True runs the saddlepoint pass on the
         same selection in the same call and fills neglog10p_spa, spa_state and t_hat as score_test_spa does."""
         from .assoc import AssocResult
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        eta = np.ascontiguousarray(eta, dtype=np.float64)
-        for name, v in (("A", A), ("w", w), ("eta", eta)):
-            if v.shape != (self.n,):
-                raise DimensionMismatch(f"{name} has shape {v.shape}, expected ({self.n},)")
-        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
-        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
-        if Z.ndim != 2 or Z.shape[0] != self.n:
-            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
-        z = np.empty(self.p); beta = np.empty(self.p); se = np.empty(self.p); nlp = np.empty(self.p)
+        A, w, Z, eta = _scan_args(self.n, A, w, Z, eta=np.asarray(eta, dtype=np.float64))
+        z, beta, se, nlp = _plain_out(self.p)
         bf = np.empty(self.p); sf = np.empty(self.p); nf = np.empty(self.p)
         fstate = np.empty(self.p, dtype=np.uint8)
         fevals = np.empty(self.p, dtype=np.int32)
-        sv = np.empty(self.p) if spa else None
-        state = np.empty(self.p, dtype=np.uint8) if spa else None
-        that = np.empty((self.p, 2), order="F") if spa else None
+        sp = _spa_out(self.p, on=spa)
         _check(lib().mih_assoc_score_firth(self._h, _p(A), _p(w), _p(Z), Z.shape[1], _p(eta), float(cutoff), int(slice_rows),
                                            _p(z), _p(beta), _p(se), _p(nlp), _p(bf), _p(sf), _p(nf), _p(fstate), _p(fevals),
-                                           _p(sv), _p(state), _p(that)))
-        return AssocResult(z, beta, se, nlp, neglog10p_spa=sv, spa_state=state, t_hat=that, beta_firth=bf, se_firth=sf,
-                           neglog10p_firth=nf, firth_state=fstate, firth_evals=fevals)
+                                           *map(_p, sp.values())))
+        return AssocResult(z, beta, se, nlp, beta_firth=bf, se_firth=sf, neglog10p_firth=nf, firth_state=fstate, firth_evals=fevals, **sp)
 
     def assoc(self, y, z=None, *, d=None, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0):
         """The marginal association scan: the null model y ~ z (fit_null; z=None: an intercept) and the score test of every column
@@ -524,50 +541,43 @@ class _Mat:
         (score_test_spa).  firth=True (likewise): the Firth-penalised effect size and likelihood-ratio p-value of the columns with
         |z| >= firth_cutoff (score_test_firth); with spa=True too both run in one call, on one selection: spa_cutoff must then
         equal firth_cutoff."""
-        from .assoc import fit_null
         d = Normal() if d is None else _inst(d)
-        if spa or firth:
-            opt = "firth=True" if firth else "spa=True"
+        opt = "firth=True" if firth else "spa=True" if spa else None
+        if opt:
             if not isinstance(d, Bernoulli) or (l is not None and _inst(l).code != 1):
                 raise ArgumentError(f"{opt} is offered for a Bernoulli trait with the logit link only, got "
                                     f"{type(d).__name__}" + ("" if l is None else f" with {type(_inst(l)).__name__}"))
             if spa and firth and float(spa_cutoff) != float(firth_cutoff):
                 raise ArgumentError(f"spa=True with firth=True runs both passes on one selection: spa_cutoff ({spa_cutoff}) "
                                     f"must equal firth_cutoff ({firth_cutoff})")
-            y = np.asarray(y, dtype=np.float64)
-            if y.ndim != 1:
-                raise ArgumentError(f"{opt} takes one trait")
-            if y.shape[0] != self.n:
-                raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
-            zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
-            null = fit_null(y, zc, d, l)
-            if firth:
-                res = self.score_test_firth(null.A, null.w, zc, null.eta, firth_cutoff, slice_rows, spa=bool(spa))
-            else:
-                res = self.score_test_spa(null.A, null.w, zc, null.eta, spa_cutoff, slice_rows)
-            res.null = null
-            return res
+        y, zc = self._trait_args(y, z, d, opt)
+        null, A, w, rt = _null_scores(y, zc, d, l)
+        if firth:
+            res = self.score_test_firth(A, w, zc, null.eta, firth_cutoff, slice_rows, spa=bool(spa))
+        elif spa:
+            res = self.score_test_spa(A, w, zc, null.eta, spa_cutoff, slice_rows)
+        else:
+            res = self.score_test(A, w, zc, slice_rows)
+        if rt is not None:
+            res.beta = res.beta * rt[None, :]
+            res.se = res.se[:, None] * rt[None, :]
+            if y.ndim == 1:
+                null = null[0]
+                res.z, res.beta, res.se, res.neglog10p = res.z[:, 0].copy(), res.beta[:, 0].copy(), res.se[:, 0].copy(), res.neglog10p[:, 0].copy()
+        res.null = null
+        return res
+
+    def _trait_args(self, y, z, d, one=None):
+        """y (n, or n x t for Normal traits; one: the caller or option that takes one trait only) and the covariates (None: an
+        intercept) as fit_null takes them."""
         y = np.asarray(y, dtype=np.float64)
-        zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
+        if one is not None and y.ndim != 1:
+            raise ArgumentError(f"{one} takes one trait")
         if y.ndim == 2 and not isinstance(d, Normal):
             raise ArgumentError("several traits at once are offered for Normal traits only")
         if y.shape[0] != self.n:
             raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
-        if isinstance(d, Normal) and (l is None or _inst(l).code == 0):
-            nulls = [fit_null(col, zc, d, l) for col in (y.T if y.ndim == 2 else [y])]
-            rt = np.sqrt(np.array([m.phi for m in nulls]))
-            A = np.stack([(col - m.mu) / r for col, m, r in zip((y.T if y.ndim == 2 else [y]), nulls, rt)], axis=1)
-            res = self.score_test(A, None, zc, slice_rows)        # unit weights; z is exact this way, beta and se take the trait's sqrt(phi)
-            res.beta = res.beta * rt[None, :]
-            res.se = res.se[:, None] * rt[None, :]
-            if y.ndim == 1:
-                res.z, res.beta, res.se, res.neglog10p = res.z[:, 0].copy(), res.beta[:, 0].copy(), res.se[:, 0].copy(), res.neglog10p[:, 0].copy()
-            res.null = nulls if y.ndim == 2 else nulls[0]
-            return res
-        null = fit_null(y, zc, d, l)
-        res = self.score_test(null.A, null.w, zc, slice_rows)
-        res.null = null
-        return res
+        return y, np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
 
     def set_test(self, A, w, Z, sets, omega=None, slice_rows=0, cov=False):
         """Burden and SKAT tests of sets of columns on top of the score test of every column -- mih_assoc_sets as it is: score
@@ -577,17 +587,7 @@ class _Mat:
         Returns a SetResult; cov=True also keeps every set's covariance K of the scores (a list of m_s x m_s arrays over the
         entries, NaN in the rows and columns of entries that are not members)."""
         from .assoc import AssocResult, SetResult
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        if A.shape != (self.n,):
-            raise DimensionMismatch(f"A has shape {A.shape}, expected ({self.n},)")
-        Z = np.ones((self.n, 1)) if Z is None else np.asarray(Z, dtype=np.float64)
-        Z = np.asfortranarray(Z.reshape(self.n, -1) if Z.ndim == 1 else Z)
-        if Z.ndim != 2 or Z.shape[0] != self.n:
-            raise DimensionMismatch(f"Z has shape {Z.shape}, expected {self.n} rows")
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64)
-            if w.shape != (self.n,):
-                raise DimensionMismatch(f"w has shape {w.shape}, expected ({self.n},)")
+        A, w, Z, _ = _scan_args(self.n, A, w, Z)
         if isinstance(sets, tuple):                     # a tuple is (set_ptr, set_col), a list is a list of sets
             if len(sets) != 2:
                 raise ArgumentError("sets as a tuple must be (set_ptr, set_col)")
@@ -614,7 +614,7 @@ class _Mat:
         om = np.ascontiguousarray(om, dtype=np.float64)
         if om.size != col.size:
             raise DimensionMismatch(f"omega has {om.size} entries, the sets have {col.size}")
-        z = np.empty(self.p); beta = np.empty(self.p); se = np.empty(self.p); nlp = np.empty(self.p)
+        z, beta, se, nlp = _plain_out(self.p)
         k = max(ns, 0)
         m_used = np.empty(k, dtype=np.int32); state = np.empty(k, dtype=np.uint8)
         bz = np.empty(k); bn = np.empty(k); sq = np.empty(k); sn = np.empty(k)
@@ -639,14 +639,8 @@ class _Mat:
         flags of the handle.  weights may be an array of p weights instead (used as they are; a DenseMatrix, which has no allele
         frequencies, takes only that).  max_maf: entries whose minor allele frequency is above it (or not a number) are dropped
         from their sets.  Returns a SetResult whose `assoc.null` is the NullModel."""
-        from .assoc import fit_null
         d = Normal() if d is None else _inst(d)
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1:
-            raise ArgumentError("assoc_sets takes one trait")
-        if y.shape[0] != self.n:
-            raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
-        zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
+        y, zc = self._trait_args(y, z, d, "assoc_sets")
         parts = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
         for q in parts:
             if q.size and (q.min() < 0 or q.max() >= self.p):
@@ -676,14 +670,11 @@ class _Mat:
             if not has_maf:
                 raise ArgumentError("a DenseMatrix has no allele frequencies: max_maf cannot be applied")
             parts = [q[maf[q] <= float(max_maf)] for q in parts]
-        null = fit_null(y, zc, d, l)
-        if isinstance(d, Normal) and (l is None or _inst(l).code == 0):
-            A, w = (y - null.mu) / math.sqrt(null.phi), None
-        else:
-            A, w = null.A, null.w
+        null, A, w, rt = _null_scores(y, zc, d, l)
+        if rt is not None:
+            null, A, rt = null[0], A[:, 0], rt[0]
         res = self.set_test(A, w, zc, parts, [om[q] for q in parts], slice_rows=slice_rows, cov=cov)
-        if w is None:
-            rt = math.sqrt(null.phi)
+        if rt is not None:
             res.assoc.beta, res.assoc.se = res.assoc.beta * rt, res.assoc.se * rt
         res.assoc.null = null
         return res
@@ -2065,12 +2056,7 @@ def gwas(plinkfile, d, *, phenotypes=6, covariates="", outfile="gwas.txt", exclu
         raise ArgumentError("gwas scans one phenotype at a time")
     if l is None:
         l = LogLink() if isinstance(d, NegativeBinomial) else canonicallink(d)
-    if firth:
-        res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=bool(spa), spa_cutoff=spa_cutoff, firth=True, firth_cutoff=firth_cutoff)
-    elif spa:
-        res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=True, spa_cutoff=spa_cutoff)
-    else:
-        res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows)
+    res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=bool(spa), spa_cutoff=spa_cutoff, firth=bool(firth), firth_cutoff=firth_cutoff)
     if outfile:
         chrom, pos, ids, a1, a2 = info
         with open(outfile, "w") as f:

@@ -10,8 +10,7 @@
 // class.  Everything up to one rounding per class sum is an integer: no result depends on how the rows are cut into slices.
 #include "grm.h"
 #include "normal_tail.h"
-#include "assoc_spa.h"
-#include "assoc_sets.h"
+#include "assoc.h"
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -326,18 +325,48 @@ static bool assoc_null_factor(const double *Z, const double *w, int64_t n, int c
 
 static unsigned blocks_of(int64_t items) { return (unsigned)((items + 255) / 256); }
 
-// what mih_assoc_score_spa adds to a call (nullptr: no saddlepoint pass)
-struct SpaCall { const double *eta; double cutoff; double *neglog10p_spa; uint8_t *state; double *t_hat; };
-// what mih_assoc_score_firth adds to a call (nullptr: no Firth pass); with a SpaCall beside it both passes run on one selection
-struct FirthCall { const double *eta; double cutoff; double *beta, *se, *neglog10p; uint8_t *state; int32_t *evals; };
+// A call as its entry point states it: mih_assoc_score's arguments, and what the other three add (nullptr: that pass does not run)
+struct AssocCall {
+    const mih_mat *h; const double *A; int32_t t; const double *w, *Z; int32_t c; int64_t slice_rows;
+    double *z, *beta, *se, *neglog10p, *wsum;
+    const SpaCall *spa; const FirthCall *firth; const SetsCall *sets;
+    // the entry point that the texts about eta, the cutoff and the selection name
+    const char *who() const { return firth ? "mih_assoc_score_firth" : "mih_assoc_score_spa"; }
+    const double *eta() const { return firth ? firth->eta : spa ? spa->eta : nullptr; }
+};
 
-// the body of the four entry points (sets: what mih_assoc_sets adds, nullptr: no set pass)
-static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
-                           double *z, double *beta, double *se, double *neglog10p, double *wsum, const SpaCall *spa, const FirthCall *firth = nullptr, const SetsCall *sets = nullptr)
+// What the steps of a call hand on to the later ones, each group filled by the step named beside it.  The host arrays that an
+// asynchronous upload reads live here, until the call returns.
+struct AssocWork {
+    double wmax = 0.0;                           // assoc_refuse
+    std::vector<double> Linv;
+    bool snp = false, classes = false;           // assoc_slice_plan: a 2-bit handle; ... with weights, which takes the class kernel
+    int64_t bps = 0, nsl = 1;                    // block pairs of a row slice, slices
+    std::vector<uint8_t> deg;                    // assoc_degenerate
+    std::vector<int32_t> counts;
+    int e = 0;                                   // assoc_fixed_weights
+    std::vector<unsigned long long> Rw;
+    U128 rsum = {0ull, 0ull};
+    DevBuf<double> Ad, Zd, wd, R, S, Q, V, Ld, Wc, zd, bd, sd;     // assoc_linear; Wc, Rd, tm, dig, part: assoc_q
+    DevBuf<uint8_t> degd;
+    DevBuf<unsigned long long> Rd, tm;
+    DevBuf<uint32_t> dig;
+    DevBuf<int32_t> part;
+    XtvWork xw;
+    std::vector<double> ones;
+    std::vector<double> hz, hb, hs, hw, hn;      // assoc_finish: z, beta, se, the class sums, neglog10p on the host
+};
+
+// ---- refusals: host only, nothing allocated, nothing written ----
+static int assoc_refuse(const AssocCall &a, AssocWork &k)
 {
-    const char *who = firth ? "mih_assoc_score_firth" : "mih_assoc_score_spa";
-    // ---- refusals: nothing allocated, nothing written ----
-    if (!h || !A || !Z || !z || !beta || !se || !neglog10p) { set_error("mih_assoc_score: null argument"); return MIH_BAD_ARG; }
+    const mih_mat *h = a.h;
+    const double *A = a.A, *w = a.w, *Z = a.Z, *eta = a.eta();
+    const int32_t t = a.t, c = a.c;
+    const SpaCall *spa = a.spa;
+    const FirthCall *firth = a.firth;
+    const char *who = a.who();
+    if (!h || !A || !Z || !a.z || !a.beta || !a.se || !a.neglog10p) { set_error("mih_assoc_score: null argument"); return MIH_BAD_ARG; }
     if (spa) {
         if (!w || !spa->eta || !spa->neglog10p_spa || !spa->state) { set_error("%s: null argument", who); return MIH_BAD_ARG; }
         if (!(spa->cutoff >= 0.0)) { set_error("%s: cutoff must not be negative or NaN, got %g", who, spa->cutoff); return MIH_BAD_ARG; }
@@ -346,13 +375,12 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
         if (!w || !firth->eta || !firth->beta || !firth->se || !firth->neglog10p || !firth->state) { set_error("%s: null argument", who); return MIH_BAD_ARG; }
         if (!(firth->cutoff >= 0.0)) { set_error("%s: cutoff must not be negative or NaN, got %g", who, firth->cutoff); return MIH_BAD_ARG; }
     }
-    const double *eta = firth ? firth->eta : spa ? spa->eta : nullptr;
     if (t < 1 || t > 32) { set_error("mih_assoc_score: 1 <= t <= 32 traits, got %d", (int)t); return MIH_BAD_ARG; }
     if (c < 1 || c > 64) { set_error("mih_assoc_score: 1 <= c <= 64 covariates, got %d", (int)c); return MIH_BAD_ARG; }
-    if (slice_rows < 0) { set_error("mih_assoc_score: slice_rows must not be negative, got %lld", (long long)slice_rows); return MIH_BAD_ARG; }
+    if (a.slice_rows < 0) { set_error("mih_assoc_score: slice_rows must not be negative, got %lld", (long long)a.slice_rows); return MIH_BAD_ARG; }
     const int64_t n = h->n, p = h->p;
     if (n < 1 || p < 1) { set_error("mih_assoc_score: an empty matrix"); return MIH_BAD_DIM; }
-    double wmax = 0.0;
+    double wmax = 0.0;                           // the fixed-point scale needs the maximum, and this loop has it
     if (w)
         for (int64_t i = 0; i < n; ++i) {
             if (!(w[i] >= 0.0) || !std::isfinite(w[i])) { set_error("mih_assoc_score: weight %lld is negative or not finite", (long long)i + 1); return MIH_BAD_ARG; }
@@ -361,17 +389,22 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
     if (!all_finite(A, (size_t)n * (size_t)t)) { set_error("mih_assoc_score: a score residual is not finite"); return MIH_BAD_ARG; }
     if (!all_finite(Z, (size_t)n * (size_t)c)) { set_error("mih_assoc_score: a covariate is not finite"); return MIH_BAD_ARG; }
     if (eta && !all_finite(eta, (size_t)n)) { set_error("%s: a linear predictor is not finite", who); return MIH_BAD_ARG; }
-    if (sets) MIH_TRY(assoc_sets_check(*sets, p));
-    std::vector<double> Linv;
-    if (!assoc_null_factor(Z, w, n, c, Linv)) { set_error("mih_assoc_score: Z'WZ is not positive definite"); return MIH_BAD_ARG; }
+    if (a.sets) MIH_TRY(assoc_sets_check(*a.sets, p));
+    if (!assoc_null_factor(Z, w, n, c, k.Linv)) { set_error("mih_assoc_score: Z'WZ is not positive definite"); return MIH_BAD_ARG; }
+    k.wmax = wmax;
+    return MIH_OK;
+}
 
-    const int m = t + c;
-    const bool snp = h->kind == 0, classes = snp && w != nullptr;
-    const int64_t nbp = h->nbp, ncg = h->ncg, nblk = 2 * nbp;
-    // the row slices of the class kernel: never longer than the exact range of an f32 accumulator, whatever the caller asks for
+// ---- the slice plan: the row slices of the class kernel, never longer than the exact range of an f32 accumulator, whatever the
+// caller asks for ----
+static int assoc_slice_plan(const AssocCall &a, AssocWork &k)
+{
+    const mih_mat *h = a.h;
+    const int64_t slice_rows = a.slice_rows, nbp = h->nbp, ncg = h->ncg;
+    k.snp = h->kind == 0; k.classes = k.snp && a.w != nullptr;
     int64_t bps = slice_rows > 0 ? std::min(kAssocSliceBp, (std::min(slice_rows, kAssocSliceBp * 128) + 127) / 128) : kAssocSliceBp;
     int64_t nsl = 1;
-    if (classes) {
+    if (k.classes) {
         const int64_t ngp = (ncg + 1) / 2;
         if (slice_rows == 0) {          // a launch with few column groups: more, shorter slices (the sums are integers: same bits)
             const int64_t want = (kAssocWaves + ngp - 1) / ngp;
@@ -384,8 +417,21 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
             return MIH_BAD_DIM;
         }
     }
+    k.bps = bps; k.nsl = nsl;
+    return MIH_OK;
+}
 
-    // ---- the memory rule: everything the call will hold beyond the handle, against what the device has free ----
+// ---- the memory rule: everything the call will hold beyond the handle, against what the device has free ----
+static int assoc_memory_rule(const AssocCall &a, const AssocWork &k)
+{
+    const mih_mat *h = a.h;
+    const SpaCall *spa = a.spa;
+    const FirthCall *firth = a.firth;
+    const SetsCall *sets = a.sets;
+    const int32_t t = a.t, c = a.c;
+    const int m = t + c;
+    const bool snp = k.snp, classes = k.classes;
+    const int64_t n = h->n, p = h->p, ncg = h->ncg, nblk = 2 * h->nbp, nsl = k.nsl;
     MIH_HIP(hipSetDevice(h->device));
     const double dn = (double)n, dp = (double)p;
     double need = 8.0 * dn * (2.0 * m + 1.0)                               // A, Z, w and R = [A | w o Z]
@@ -424,148 +470,189 @@ static int assoc_score_run(const mih_mat *h, const double *A, int32_t t, const d
                   (int)t, (int)c, (long long)n, (long long)p, need, (double)free_b);
         return MIH_OOM;
     }
+    return MIH_OK;
+}
 
+// ---- the degenerate columns of a 2-bit handle, decided in integers: no observed genotype, or one class holds all observed ones ----
+static int assoc_degenerate(const AssocCall &a, AssocWork &k)
+{
+    const int64_t p = a.h->p;
+    k.deg.assign((size_t)p, 0);
+    if (!k.snp) return MIH_OK;
+    std::vector<int32_t> &counts = k.counts;
+    counts.resize((size_t)(4 * p));
+    MIH_TRY(mih_snp_counts(a.h, nullptr, nullptr, counts.data(), nullptr));
+    for (int64_t j = 0; j < p; ++j) {
+        const int64_t n0 = counts[4 * j], n1 = counts[4 * j + 1], n2 = counts[4 * j + 2], nobs = n0 + n1 + n2;
+        k.deg[(size_t)j] = (nobs == 0 || n0 == nobs || n1 == nobs || n2 == nobs) ? 1 : 0;
+    }
+    return MIH_OK;
+}
+
+// ---- the fixed-point weights R_i = rint(w_i 2^e), max w 2^e < 2^54, and their sum (host) ----
+static void assoc_fixed_weights(const AssocCall &a, AssocWork &k)
+{
+    if (!k.classes) return;
+    if (k.wmax > 0.0) k.e = std::min(kAssocEbits - std::ilogb(k.wmax), 1000);
+    k.Rw.assign((size_t)a.h->n_pad, 0ull);
+    for (int64_t i = 0; i < a.h->n; ++i) {
+        k.Rw[(size_t)i] = (unsigned long long)std::llrint(std::ldexp(a.w[i], k.e));
+        k.rsum = u128_add(k.rsum, U128{0ull, k.Rw[(size_t)i]});
+    }
+}
+
+// ---- the uploads, and the linear terms: one fused X'R over [A | w o Z] into S ----
+static int assoc_linear(const AssocCall &a, AssocWork &k)
+{
+    const mih_mat *h = a.h;
     hipStream_t s = h->stream;
-    // degenerate columns of a 2-bit handle, decided in integers: no observed genotype, or one class holds all observed ones
-    std::vector<uint8_t> deg((size_t)p, 0);
-    std::vector<int32_t> counts;
-    if (snp) {
-        counts.resize((size_t)(4 * p));
-        MIH_TRY(mih_snp_counts(h, nullptr, nullptr, counts.data(), nullptr));
-        for (int64_t j = 0; j < p; ++j) {
-            const int64_t n0 = counts[4 * j], n1 = counts[4 * j + 1], n2 = counts[4 * j + 2], nobs = n0 + n1 + n2;
-            deg[(size_t)j] = (nobs == 0 || n0 == nobs || n1 == nobs || n2 == nobs) ? 1 : 0;
-        }
-    }
-    // the fixed-point weights R_i = rint(w_i 2^e), max w 2^e < 2^54 (host: the scale needs the maximum, which the checks have)
-    int e = 0;
-    std::vector<unsigned long long> Rw;
-    U128 rsum = {0ull, 0ull};
-    if (classes) {
-        if (wmax > 0.0) e = std::min(kAssocEbits - std::ilogb(wmax), 1000);
-        Rw.assign((size_t)h->n_pad, 0ull);
-        for (int64_t i = 0; i < n; ++i) {
-            Rw[(size_t)i] = (unsigned long long)std::llrint(std::ldexp(w[i], e));
-            rsum = u128_add(rsum, U128{0ull, Rw[(size_t)i]});
-        }
-    }
+    const double *w = a.w;
+    const int32_t t = a.t, c = a.c;
+    const int m = t + c;
+    const int64_t n = h->n, p = h->p;
+    MIH_TRY(k.Ad.alloc((size_t)n * t)); MIH_TRY(k.Zd.alloc((size_t)n * c)); MIH_TRY(k.wd.alloc((size_t)n)); MIH_TRY(k.R.alloc((size_t)n * m));
+    MIH_TRY(k.S.alloc((size_t)p * m)); MIH_TRY(k.Q.alloc((size_t)p)); MIH_TRY(k.V.alloc((size_t)p)); MIH_TRY(k.Ld.alloc((size_t)c * c));
+    MIH_TRY(k.zd.alloc((size_t)p * t)); MIH_TRY(k.bd.alloc((size_t)p * t)); MIH_TRY(k.sd.alloc((size_t)p)); MIH_TRY(k.degd.alloc((size_t)p));
+    MIH_TRY(xtv_work_init(h, k.xw, m, xtv_tune(0)));
+    MIH_HIP(hipMemcpyAsync(k.Ad.p, a.A, sizeof(double) * (size_t)n * t, hipMemcpyHostToDevice, s));
+    MIH_HIP(hipMemcpyAsync(k.Zd.p, a.Z, sizeof(double) * (size_t)n * c, hipMemcpyHostToDevice, s));
+    if (!w) k.ones.assign((size_t)n, 1.0);
+    MIH_HIP(hipMemcpyAsync(k.wd.p, w ? w : k.ones.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    MIH_HIP(hipMemcpyAsync(k.Ld.p, k.Linv.data(), sizeof(double) * (size_t)c * c, hipMemcpyHostToDevice, s));
+    MIH_HIP(hipMemcpyAsync(k.degd.p, k.deg.data(), (size_t)p, hipMemcpyHostToDevice, s));
 
-    DevBuf<double> Ad, Zd, wd, R, S, Q, V, Ld, Wc, zd, bd, sd;
-    DevBuf<uint8_t> degd;
-    DevBuf<unsigned long long> Rd, tm;
-    DevBuf<uint32_t> dig;
-    DevBuf<int32_t> part;
-    XtvWork xw;
-    MIH_TRY(Ad.alloc((size_t)n * t)); MIH_TRY(Zd.alloc((size_t)n * c)); MIH_TRY(wd.alloc((size_t)n)); MIH_TRY(R.alloc((size_t)n * m));
-    MIH_TRY(S.alloc((size_t)p * m)); MIH_TRY(Q.alloc((size_t)p)); MIH_TRY(V.alloc((size_t)p)); MIH_TRY(Ld.alloc((size_t)c * c));
-    MIH_TRY(zd.alloc((size_t)p * t)); MIH_TRY(bd.alloc((size_t)p * t)); MIH_TRY(sd.alloc((size_t)p)); MIH_TRY(degd.alloc((size_t)p));
-    MIH_TRY(xtv_work_init(h, xw, m, xtv_tune(0)));
-    MIH_HIP(hipMemcpyAsync(Ad.p, A, sizeof(double) * (size_t)n * t, hipMemcpyHostToDevice, s));
-    MIH_HIP(hipMemcpyAsync(Zd.p, Z, sizeof(double) * (size_t)n * c, hipMemcpyHostToDevice, s));
-    std::vector<double> ones;
-    if (!w) ones.assign((size_t)n, 1.0);
-    MIH_HIP(hipMemcpyAsync(wd.p, w ? w : ones.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    MIH_HIP(hipMemcpyAsync(Ld.p, Linv.data(), sizeof(double) * (size_t)c * c, hipMemcpyHostToDevice, s));
-    MIH_HIP(hipMemcpyAsync(degd.p, deg.data(), (size_t)p, hipMemcpyHostToDevice, s));
-
-    // ---- the linear terms: one fused X'R over [A | w o Z] ----
-    hipLaunchKernelGGL(k_assoc_rhs, dim3(blocks_of(n), (unsigned)m), dim3(256), 0, s, Ad.p, wd.p, Zd.p, n, (int)t, (int)c, R.p);
+    hipLaunchKernelGGL(k_assoc_rhs, dim3(blocks_of(n), (unsigned)m), dim3(256), 0, s, k.Ad.p, k.wd.p, k.Zd.p, n, (int)t, (int)c, k.R.p);
     MIH_TRY(launch_failed("k_assoc_rhs"));
-    MIH_TRY(xtv_device(h, xw, R.p, m, S.p, s));
+    return xtv_device(h, k.xw, k.R.p, m, k.S.p, s);
+}
 
-    // ---- Q ----
-    if (snp) {
-        MIH_TRY(Wc.alloc((size_t)(4 * p)));
-        if (classes) {
-            MIH_TRY(Rd.alloc((size_t)h->n_pad)); MIH_TRY(dig.alloc((size_t)(nblk * 64 * 4))); MIH_TRY(part.alloc((size_t)(nsl * ncg * 2048)));
-            MIH_TRY(tm.alloc((size_t)(2 * p)));
-            MIH_HIP(hipMemcpyAsync(Rd.p, Rw.data(), sizeof(unsigned long long) * (size_t)h->n_pad, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_assoc_digits, dim3(blocks_of(nblk * 64)), dim3(256), 0, s, Rd.p, n, nblk, reinterpret_cast<uint4 *>(dig.p));
-            MIH_TRY(launch_failed("k_assoc_digits"));
-            const int64_t items = (ncg + 1) / 2 * nsl;
-            PassRecord rec;
-            const bool timed = prof_begin(h, s, rec);
-            hipLaunchKernelGGL(k_assoc_classes, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X),
-                               reinterpret_cast<const uint4 *>(dig.p), nbp, ncg, bps, (int)nsl, part.p);
-            if (timed) { snprintf(rec.kernel, sizeof(rec.kernel), "k_assoc_classes"); rec.residuals = 1; rec.operands = (int)nsl; prof_end(h, s, rec); }
-            MIH_TRY(launch_failed("k_assoc_classes"));
-            hipLaunchKernelGGL(k_assoc_missing, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, s, h->miss_ptr, h->miss_row, Rd.p, p, tm.p);
-            MIH_TRY(launch_failed("k_assoc_missing"));
-            hipLaunchKernelGGL(k_assoc_wsum, dim3(blocks_of(p)), dim3(256), 0, s, part.p, (int)nsl, ncg, p, tm.p, rsum.hi, rsum.lo, e, Wc.p);
-            MIH_TRY(launch_failed("k_assoc_wsum"));
-        } else {                            // unit weights: the four class sums are the integer counts
-            std::vector<double> wc((size_t)(4 * p));
-            for (int64_t j = 0; j < 4 * p; ++j) wc[(size_t)j] = (double)counts[(size_t)j];
-            MIH_HIP(hipMemcpyAsync(Wc.p, wc.data(), sizeof(double) * (size_t)(4 * p), hipMemcpyHostToDevice, s));
-            MIH_HIP(hipStreamSynchronize(s));
-        }
-        hipLaunchKernelGGL(k_assoc_q_snp, dim3(blocks_of(p)), dim3(256), 0, s, Wc.p, h->mu, h->sinv, h->center, h->scale, h->impute, p, Q.p);
-        MIH_TRY(launch_failed("k_assoc_q_snp"));
-    } else {
-        const DosageView dv = dosage_view(h);
-        if (h->Du) hipLaunchKernelGGL(k_assoc_q_dense<2>, dim3((unsigned)p), dim3(256), 0, s, h->D, h->Df, dv, wd.p, n, Q.p);
-        else if (h->Df) hipLaunchKernelGGL(k_assoc_q_dense<1>, dim3((unsigned)p), dim3(256), 0, s, h->D, h->Df, dv, wd.p, n, Q.p);
-        else hipLaunchKernelGGL(k_assoc_q_dense<0>, dim3((unsigned)p), dim3(256), 0, s, h->D, h->Df, dv, wd.p, n, Q.p);
-        MIH_TRY(launch_failed("k_assoc_q_dense"));
+// ---- Q, three routes ----
+// 2-bit with weights: the class sums Wc from the class kernel over the fixed-point weights
+static int assoc_q_classes(const AssocCall &a, AssocWork &k)
+{
+    const mih_mat *h = a.h;
+    hipStream_t s = h->stream;
+    const int64_t n = h->n, p = h->p, nbp = h->nbp, ncg = h->ncg, nblk = 2 * nbp, nsl = k.nsl;
+    MIH_TRY(k.Rd.alloc((size_t)h->n_pad)); MIH_TRY(k.dig.alloc((size_t)(nblk * 64 * 4))); MIH_TRY(k.part.alloc((size_t)(nsl * ncg * 2048)));
+    MIH_TRY(k.tm.alloc((size_t)(2 * p)));
+    MIH_HIP(hipMemcpyAsync(k.Rd.p, k.Rw.data(), sizeof(unsigned long long) * (size_t)h->n_pad, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_assoc_digits, dim3(blocks_of(nblk * 64)), dim3(256), 0, s, k.Rd.p, n, nblk, reinterpret_cast<uint4 *>(k.dig.p));
+    MIH_TRY(launch_failed("k_assoc_digits"));
+    const int64_t items = (ncg + 1) / 2 * nsl;
+    PassRecord rec;
+    const bool timed = prof_begin(h, s, rec);
+    hipLaunchKernelGGL(k_assoc_classes, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X),
+                       reinterpret_cast<const uint4 *>(k.dig.p), nbp, ncg, k.bps, (int)nsl, k.part.p);
+    if (timed) { snprintf(rec.kernel, sizeof(rec.kernel), "k_assoc_classes"); rec.residuals = 1; rec.operands = (int)nsl; prof_end(h, s, rec); }
+    MIH_TRY(launch_failed("k_assoc_classes"));
+    hipLaunchKernelGGL(k_assoc_missing, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, s, h->miss_ptr, h->miss_row, k.Rd.p, p, k.tm.p);
+    MIH_TRY(launch_failed("k_assoc_missing"));
+    hipLaunchKernelGGL(k_assoc_wsum, dim3(blocks_of(p)), dim3(256), 0, s, k.part.p, (int)nsl, ncg, p, k.tm.p, k.rsum.hi, k.rsum.lo, k.e, k.Wc.p);
+    return launch_failed("k_assoc_wsum");
+}
+
+// 2-bit with unit weights: the four class sums are the integer counts
+static int assoc_q_counts(const AssocCall &a, AssocWork &k)
+{
+    hipStream_t s = a.h->stream;
+    const int64_t p = a.h->p;
+    std::vector<double> wc((size_t)(4 * p));
+    for (int64_t j = 0; j < 4 * p; ++j) wc[(size_t)j] = (double)k.counts[(size_t)j];
+    MIH_HIP(hipMemcpyAsync(k.Wc.p, wc.data(), sizeof(double) * (size_t)(4 * p), hipMemcpyHostToDevice, s));
+    MIH_HIP(hipStreamSynchronize(s));            // wc ends here
+    return MIH_OK;
+}
+
+static int assoc_q(const AssocCall &a, AssocWork &k)
+{
+    const mih_mat *h = a.h;
+    hipStream_t s = h->stream;
+    const int64_t n = h->n, p = h->p;
+    if (k.snp) {
+        MIH_TRY(k.Wc.alloc((size_t)(4 * p)));
+        MIH_TRY(k.classes ? assoc_q_classes(a, k) : assoc_q_counts(a, k));
+        hipLaunchKernelGGL(k_assoc_q_snp, dim3(blocks_of(p)), dim3(256), 0, s, k.Wc.p, h->mu, h->sinv, h->center, h->scale, h->impute, p, k.Q.p);
+        return launch_failed("k_assoc_q_snp");
     }
+    const DosageView dv = dosage_view(h);        // dense and dosage: straight from the entries
+    by_kind(h, [&](auto K) {
+        if constexpr (decltype(K)::value < 3)    // a 2-bit handle went the other way
+            hipLaunchKernelGGL(k_assoc_q_dense<decltype(K)::value>, dim3((unsigned)p), dim3(256), 0, s, h->D, h->Df, dv, k.wd.p, n, k.Q.p);
+    });
+    return launch_failed("k_assoc_q_dense");
+}
 
-    // ---- the finish ----
-    hipLaunchKernelGGL(k_assoc_var, dim3(blocks_of(p)), dim3(256), 0, s, S.p, p, (int)t, (int)c, Ld.p, Q.p, degd.p, V.p);
+// ---- the finish: V, then z, beta and se, and all of it on the host with the normal p-values ----
+static int assoc_finish(const AssocCall &a, AssocWork &k)
+{
+    const mih_mat *h = a.h;
+    hipStream_t s = h->stream;
+    const int32_t t = a.t, c = a.c;
+    const int64_t p = h->p;
+    hipLaunchKernelGGL(k_assoc_var, dim3(blocks_of(p)), dim3(256), 0, s, k.S.p, p, (int)t, (int)c, k.Ld.p, k.Q.p, k.degd.p, k.V.p);
     MIH_TRY(launch_failed("k_assoc_var"));
-    hipLaunchKernelGGL(k_assoc_finish, dim3(blocks_of(p * t)), dim3(256), 0, s, S.p, V.p, p, (int)t, zd.p, bd.p, sd.p);
+    hipLaunchKernelGGL(k_assoc_finish, dim3(blocks_of(p * t)), dim3(256), 0, s, k.S.p, k.V.p, p, (int)t, k.zd.p, k.bd.p, k.sd.p);
     MIH_TRY(launch_failed("k_assoc_finish"));
-    // the results reach the caller's arrays only when all of them are there
-    std::vector<double> hz((size_t)p * t), hb((size_t)p * t), hs((size_t)p), hw;
-    MIH_HIP(hipMemcpyAsync(hz.data(), zd.p, sizeof(double) * (size_t)p * t, hipMemcpyDeviceToHost, s));
-    MIH_HIP(hipMemcpyAsync(hb.data(), bd.p, sizeof(double) * (size_t)p * t, hipMemcpyDeviceToHost, s));
-    MIH_HIP(hipMemcpyAsync(hs.data(), sd.p, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
-    if (wsum && snp) {
-        hw.resize((size_t)(4 * p));
-        MIH_HIP(hipMemcpyAsync(hw.data(), Wc.p, sizeof(double) * (size_t)(4 * p), hipMemcpyDeviceToHost, s));
+    k.hz.resize((size_t)p * t); k.hb.resize((size_t)p * t); k.hs.resize((size_t)p);
+    MIH_HIP(hipMemcpyAsync(k.hz.data(), k.zd.p, sizeof(double) * (size_t)p * t, hipMemcpyDeviceToHost, s));
+    MIH_HIP(hipMemcpyAsync(k.hb.data(), k.bd.p, sizeof(double) * (size_t)p * t, hipMemcpyDeviceToHost, s));
+    MIH_HIP(hipMemcpyAsync(k.hs.data(), k.sd.p, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
+    if (a.wsum && k.snp) {
+        k.hw.resize((size_t)(4 * p));
+        MIH_HIP(hipMemcpyAsync(k.hw.data(), k.Wc.p, sizeof(double) * (size_t)(4 * p), hipMemcpyDeviceToHost, s));
     }
     MIH_HIP(hipStreamSynchronize(s));
-    std::vector<double> hn(hz.size()), spa_v, spa_t, f_b, f_se, f_n;
-    std::vector<uint8_t> spa_s, f_s;
-    std::vector<int32_t> f_e;
-    for (size_t i = 0; i < hz.size(); ++i) hn[i] = neglog10p_of_z(hz[i]);
-    if (spa || firth) {
+    k.hn.resize(k.hz.size());
+    for (size_t i = 0; i < k.hz.size(); ++i) k.hn[i] = neglog10p_of_z(k.hz[i]);
+    return MIH_OK;
+}
+
+// ---- the optional passes, on what the finish left: the two solvers on one selection, then the sets ----
+static int assoc_passes(const AssocCall &a, const AssocWork &k, SpaOut &spa_out, FirthOut &firth_out, SetsOut &sets_out)
+{
+    const AssocScan sc = {a.h, a.h->stream, (int)a.c, k.S.p, k.V.p, k.Ld.p, k.Zd.p, k.wd.p, k.zd.p, k.hb.data(), k.hs.data(), k.hn.data()};
+    if (a.spa || a.firth) {
         AssocFlagged fl;
-        MIH_TRY(assoc_flag_run(who, h, s, (int)c, S.p, zd.p, Ld.p, eta, firth ? firth->cutoff : spa->cutoff, fl));
-        if (spa) MIH_TRY(assoc_spa_run(h, s, (int)c, fl, S.p, V.p, Zd.p, hn.data(), spa_v, spa_s, spa_t));
-        if (firth) MIH_TRY(assoc_firth_run(h, s, (int)c, fl, S.p, V.p, Zd.p, hb.data(), hs.data(), hn.data(), f_b, f_se, f_n, f_s, f_e));
+        MIH_TRY(assoc_flag_run(a.who(), sc, a.eta(), a.firth ? a.firth->cutoff : a.spa->cutoff, fl));
+        if (a.spa) MIH_TRY(assoc_spa_run(sc, fl, spa_out));
+        if (a.firth) MIH_TRY(assoc_firth_run(sc, fl, firth_out));
     }
-    SetsOut so;
-    if (sets) MIH_TRY(assoc_sets_run(h, s, (int)c, S.p, V.p, Ld.p, wd.p, *sets, so));
-    memcpy(z, hz.data(), sizeof(double) * hz.size());
-    memcpy(beta, hb.data(), sizeof(double) * hb.size());
-    memcpy(se, hs.data(), sizeof(double) * hs.size());
-    memcpy(neglog10p, hn.data(), sizeof(double) * hn.size());
-    if (spa) {
-        memcpy(spa->neglog10p_spa, spa_v.data(), sizeof(double) * spa_v.size());
-        memcpy(spa->state, spa_s.data(), spa_s.size());
-        if (spa->t_hat) memcpy(spa->t_hat, spa_t.data(), sizeof(double) * spa_t.size());
-    }
-    if (firth) {
-        memcpy(firth->beta, f_b.data(), sizeof(double) * f_b.size());
-        memcpy(firth->se, f_se.data(), sizeof(double) * f_se.size());
-        memcpy(firth->neglog10p, f_n.data(), sizeof(double) * f_n.size());
-        memcpy(firth->state, f_s.data(), f_s.size());
-        if (firth->evals) memcpy(firth->evals, f_e.data(), sizeof(int32_t) * f_e.size());
-    }
-    if (sets && sets->nsets > 0) {
-        const size_t ns = (size_t)sets->nsets;
-        memcpy(sets->m_used, so.m_used.data(), sizeof(int32_t) * ns);
-        memcpy(sets->burden_z, so.burden_z.data(), sizeof(double) * ns);
-        memcpy(sets->neglog10p_burden, so.nlp_burden.data(), sizeof(double) * ns);
-        memcpy(sets->skat_q, so.skat_q.data(), sizeof(double) * ns);
-        memcpy(sets->neglog10p_skat, so.nlp_skat.data(), sizeof(double) * ns);
-        memcpy(sets->skat_state, so.state.data(), ns);
-        if (sets->lambda && !so.lambda.empty()) memcpy(sets->lambda, so.lambda.data(), sizeof(double) * so.lambda.size());
-        if (sets->cov && !so.cov.empty()) memcpy(sets->cov, so.cov.data(), sizeof(double) * so.cov.size());
-    }
-    if (wsum)
-        for (int64_t j = 0; j < p; ++j)
-            for (int k = 0; k < 3; ++k) wsum[3 * j + k] = snp ? hw[(size_t)(4 * j + 1 + k)] : std::numeric_limits<double>::quiet_NaN();
+    if (a.sets) MIH_TRY(assoc_sets_run(sc, *a.sets, sets_out));
+    return MIH_OK;
+}
+
+// ---- publish: the caller's arrays are written here and nowhere else ----
+static void assoc_publish(const AssocCall &a, const AssocWork &k)
+{
+    memcpy(a.z, k.hz.data(), sizeof(double) * k.hz.size());
+    memcpy(a.beta, k.hb.data(), sizeof(double) * k.hb.size());
+    memcpy(a.se, k.hs.data(), sizeof(double) * k.hs.size());
+    memcpy(a.neglog10p, k.hn.data(), sizeof(double) * k.hn.size());
+    if (a.wsum)
+        for (int64_t j = 0; j < a.h->p; ++j)
+            for (int q = 0; q < 3; ++q) a.wsum[3 * j + q] = k.snp ? k.hw[(size_t)(4 * j + 1 + q)] : std::numeric_limits<double>::quiet_NaN();
+}
+
+// the body of the four entry points; the results reach the caller's arrays only when all of them are there
+static int assoc_score_run(const AssocCall &a)
+{
+    AssocWork k;
+    MIH_TRY(assoc_refuse(a, k));
+    MIH_TRY(assoc_slice_plan(a, k));
+    MIH_TRY(assoc_memory_rule(a, k));
+    MIH_TRY(assoc_degenerate(a, k));
+    assoc_fixed_weights(a, k);
+    MIH_TRY(assoc_linear(a, k));
+    MIH_TRY(assoc_q(a, k));
+    MIH_TRY(assoc_finish(a, k));
+    SpaOut spa_out;
+    FirthOut firth_out;
+    SetsOut sets_out;
+    MIH_TRY(assoc_passes(a, k, spa_out, firth_out, sets_out));
+    assoc_publish(a, k);
+    if (a.spa) spa_publish(*a.spa, spa_out);
+    if (a.firth) firth_publish(*a.firth, firth_out);
+    if (a.sets) sets_publish(*a.sets, sets_out);
     return MIH_OK;
 }
 
@@ -578,7 +665,7 @@ extern "C" {
 int mih_assoc_score(const mih_mat *h, const double *A, int32_t t, const double *w, const double *Z, int32_t c, int64_t slice_rows,
                     double *z, double *beta, double *se, double *neglog10p, double *wsum)
 {
-    return assoc_score_run(h, A, t, w, Z, c, slice_rows, z, beta, se, neglog10p, wsum, nullptr);
+    return assoc_score_run(AssocCall{h, A, t, w, Z, c, slice_rows, z, beta, se, neglog10p, wsum, nullptr, nullptr, nullptr});
 }
 
 int mih_assoc_score_spa(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, const double *eta, double cutoff,
@@ -586,7 +673,7 @@ int mih_assoc_score_spa(const mih_mat *h, const double *A, const double *w, cons
                         double *t_hat)
 {
     const SpaCall spa = {eta, cutoff, neglog10p_spa, state, t_hat};
-    return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, &spa);
+    return assoc_score_run(AssocCall{h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, &spa, nullptr, nullptr});
 }
 
 int mih_assoc_score_firth(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, const double *eta, double cutoff,
@@ -596,7 +683,7 @@ int mih_assoc_score_firth(const mih_mat *h, const double *A, const double *w, co
 {
     const FirthCall firth = {eta, cutoff, beta_firth, se_firth, neglog10p_firth, firth_state, firth_evals};
     const SpaCall spa = {eta, cutoff, neglog10p_spa, spa_state, t_hat};
-    return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, neglog10p_spa ? &spa : nullptr, &firth);
+    return assoc_score_run(AssocCall{h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, neglog10p_spa ? &spa : nullptr, &firth, nullptr});
 }
 
 int mih_assoc_sets(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, int64_t slice_rows, int32_t nsets,
@@ -605,7 +692,7 @@ int mih_assoc_sets(const mih_mat *h, const double *A, const double *w, const dou
                    double *lambda, double *cov)
 {
     const SetsCall sets = {nsets, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambda, cov};
-    return assoc_score_run(h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, nullptr, nullptr, &sets);
+    return assoc_score_run(AssocCall{h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, nullptr, nullptr, &sets});
 }
 
 }  // extern "C"

@@ -20,7 +20,8 @@
 // from LDS and makes the same step.  All sums of a column are made inside one workgroup and U, b, V are bit-reproducible, so the
 // Firth outputs, the evaluation counts included, are bit for bit the same whatever slice_rows and the number of workgroups, and
 // on repeated calls.
-#include "assoc_spa.h"
+#include "assoc_slab.h"
+#include "firth_finish.h"
 #include <cmath>
 #include <limits>
 #include <vector>
@@ -62,7 +63,7 @@ __device__ __forceinline__ void firth_pass(const double *cs, const double *__res
 // fits 111 (dense, dosage) and 120 (2-bit) without scratch.
 template <int KIND>      // 0: f64, 1: f32, 2: dosage, 3: 2-bit
 __global__ void __launch_bounds__(256, 4)
-k_assoc_firth(SpaMat m, int64_t n, int64_t p, int c, const int64_t *__restrict__ idx, int64_t nflag, const double *__restrict__ alpha,
+k_assoc_firth(ColView m, int64_t n, int64_t p, int c, const int64_t *__restrict__ idx, int64_t nflag, const double *__restrict__ alpha,
               const double *__restrict__ Z, const double *__restrict__ eta, const double *__restrict__ mu, const double *__restrict__ sp0,
               const double *__restrict__ S, const double *__restrict__ V, double *__restrict__ slab, double *__restrict__ rec,
               int32_t *__restrict__ st)
@@ -120,47 +121,30 @@ double assoc_firth_bytes(int64_t p)
     return (double)p * (48.0 + 8.0);                         // the roots' values and their status words, had every column been flagged
 }
 
-int assoc_firth_run(const mih_mat *h, hipStream_t s, int c, const AssocFlagged &fl, const double *S, const double *V, const double *Z,
-                    const double *beta, const double *se, const double *nlp, std::vector<double> &beta_f, std::vector<double> &se_f,
-                    std::vector<double> &nlp_f, std::vector<uint8_t> &state, std::vector<int32_t> &evals)
+int assoc_firth_run(const AssocScan &sc, const AssocFlagged &fl, FirthOut &out)
 {
-    const int64_t n = h->n, p = h->p, nflag = fl.nflag, grid = fl.grid;
-    beta_f.assign(beta, beta + p);
-    se_f.assign(se, se + p);
-    nlp_f.assign(nlp, nlp + p);
-    state.assign((size_t)p, 0);
-    evals.assign((size_t)p, 0);
+    const mih_mat *h = sc.h;
+    hipStream_t s = sc.s;
+    const int64_t p = h->p, nflag = fl.nflag;
+    out.beta.assign(sc.beta, sc.beta + p);
+    out.se.assign(sc.se, sc.se + p);
+    out.nlp.assign(sc.nlp, sc.nlp + p);
+    out.state.assign((size_t)p, 0);
+    out.evals.assign((size_t)p, 0);
     if (nflag == 0) return MIH_OK;
 
-    DevBuf<double> rec;
-    DevBuf<int32_t> st;
-    MIH_TRY(rec.alloc((size_t)(6 * nflag))); MIH_TRY(st.alloc((size_t)(2 * nflag)));
-    SpaMat m = assoc_spa_mat(h);
-    PassRecord pr;
-    const bool timed = prof_begin(h, s, pr);
-#define MIH_FIRTH_LAUNCH(KIND) hipLaunchKernelGGL(k_assoc_firth<KIND>, dim3((unsigned)grid), dim3(256), 0, s, m, n, p, c, fl.idx.p, nflag, fl.alpha.p, Z, \
-                                                  fl.eta.p, fl.mu.p, fl.sp0.p, S, V, fl.slab.p, rec.p, st.p)
-    if (h->kind == 0) MIH_FIRTH_LAUNCH(3);
-    else if (h->Du) MIH_FIRTH_LAUNCH(2);
-    else if (h->Df) MIH_FIRTH_LAUNCH(1);
-    else MIH_FIRTH_LAUNCH(0);
-#undef MIH_FIRTH_LAUNCH
-    if (timed) { snprintf(pr.kernel, sizeof(pr.kernel), "k_assoc_firth"); pr.residuals = 1; pr.operands = (int)std::min<int64_t>(nflag, 2147483647); prof_end(h, s, pr); }
-    MIH_TRY(launch_failed("k_assoc_firth"));
-
-    std::vector<double> hrec((size_t)(6 * nflag));
-    std::vector<int32_t> hst((size_t)(2 * nflag));
-    MIH_HIP(hipMemcpyAsync(hrec.data(), rec.p, sizeof(double) * hrec.size(), hipMemcpyDeviceToHost, s));
-    MIH_HIP(hipMemcpyAsync(hst.data(), st.p, sizeof(int32_t) * hst.size(), hipMemcpyDeviceToHost, s));
-    MIH_HIP(hipStreamSynchronize(s));
+    std::vector<double> hrec;
+    std::vector<int32_t> hst;
+    MIH_TRY(assoc_solver_launch(sc, fl, "k_assoc_firth", 6, 2, [](auto K) { return k_assoc_firth<decltype(K)::value>; }, hrec, hst));
 
     int64_t total = 0;
     for (int64_t f = 0; f < nflag; ++f) {
         const int64_t j = fl.hidx[(size_t)f];
         const double *r = &hrec[(size_t)(6 * f)];
         const FirthRoot root = {r[2], r[3], r[4], r[5], (int)hst[(size_t)(2 * f)], (int)hst[(size_t)(2 * f + 1)]};
-        state[(size_t)j] = (uint8_t)firth_column(root, r[0], r[1], beta[j], se[j], nlp[j], &beta_f[(size_t)j], &se_f[(size_t)j], &nlp_f[(size_t)j]);
-        evals[(size_t)j] = root.evals;
+        out.state[(size_t)j] = (uint8_t)firth_column(root, r[0], r[1], sc.beta[j], sc.se[j], sc.nlp[j], &out.beta[(size_t)j], &out.se[(size_t)j],
+                                                     &out.nlp[(size_t)j]);
+        out.evals[(size_t)j] = root.evals;
         total += root.evals;
     }
     // a record without a kernel for the measurement hook: the columns tried and the evaluations they took
@@ -171,6 +155,15 @@ int assoc_firth_run(const mih_mat *h, hipStream_t s, int c, const AssocFlagged &
         prof_end(h, s, er);
     }
     return MIH_OK;
+}
+
+void firth_publish(const FirthCall &call, const FirthOut &out)
+{
+    memcpy(call.beta, out.beta.data(), sizeof(double) * out.beta.size());
+    memcpy(call.se, out.se.data(), sizeof(double) * out.se.size());
+    memcpy(call.neglog10p, out.nlp.data(), sizeof(double) * out.nlp.size());
+    memcpy(call.state, out.state.data(), out.state.size());
+    if (call.evals) memcpy(call.evals, out.evals.data(), sizeof(int32_t) * out.evals.size());
 }
 
 }  // namespace mih

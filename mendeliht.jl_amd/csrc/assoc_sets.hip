@@ -12,7 +12,7 @@
 // and the host finishes with mixture_tail.h.  Nothing in it depends on slice_rows, on the position of a set in the list or on the
 // other sets of the call: every C_jk is ONE chain of fused multiply-adds over the rows in ascending order (no split over rows, no
 // atomics), everything after it has a fixed operation order with contraction off.
-#include "assoc_sets.h"
+#include "assoc_slab.h"
 #include "mixture_tail.h"
 #include "sym_eig.h"
 #include <cmath>
@@ -54,7 +54,7 @@ k_assoc_set_u(const double *__restrict__ S, int64_t p, int c, const double *__re
 // D[(l >> 4) + 4 reg][l & 15] -- the C/D map grm.hip documents.  C_jk (j > k) goes to Kb[koff[s] + j m + k]: compact, m x m.
 template <int KIND>      // 0: f64, 1: f32, 2: dosage, 3: 2-bit
 __global__ void __launch_bounds__(256)
-k_assoc_set_gram(SpaMat mt, int64_t n, const int64_t *__restrict__ set_ptr, const int32_t *__restrict__ set_col, const double *__restrict__ omega,
+k_assoc_set_gram(ColView mt, int64_t n, const int64_t *__restrict__ set_ptr, const int32_t *__restrict__ set_col, const double *__restrict__ omega,
                  const double *__restrict__ V, const double *__restrict__ w, const int64_t *__restrict__ koff, int32_t *__restrict__ m_used,
                  int32_t *__restrict__ mlist, double *__restrict__ Kb)
 {
@@ -382,9 +382,12 @@ double assoc_sets_bytes(const SetsCall &sc, int c, double *resident)
          + ns * (8.0 + 8.0 + 8.0 + 4.0 + 24.0) + 64.0;                 // set_ptr, the two offsets, m_used, T / S / Q
 }
 
-int assoc_sets_run(const mih_mat *h, hipStream_t s, int c, const double *S, const double *V, const double *Linv, const double *w,
-                   const SetsCall &sc, SetsOut &out)
+int assoc_sets_run(const AssocScan &scan, const SetsCall &sc, SetsOut &out)
 {
+    const mih_mat *h = scan.h;
+    hipStream_t s = scan.s;
+    const int c = scan.c;
+    const double *S = scan.S, *V = scan.V;
     const int64_t n = h->n, p = h->p, ns = sc.nsets;
     const int64_t nent = ns ? sc.set_ptr[ns] : 0;
     out.m_used.assign((size_t)ns, 0); out.state.assign((size_t)ns, 0);
@@ -410,19 +413,16 @@ int assoc_sets_run(const mih_mat *h, hipStream_t s, int c, const double *S, cons
         MIH_HIP(hipMemcpyAsync(col_d.p, sc.set_col, sizeof(int32_t) * (size_t)nent, hipMemcpyHostToDevice, s));
         MIH_HIP(hipMemcpyAsync(om_d.p, sc.omega, sizeof(double) * (size_t)nent, hipMemcpyHostToDevice, s));
         MIH_HIP(hipMemsetAsync(mlist_d.p, 0, sizeof(int32_t) * (size_t)nent, s));
-        hipLaunchKernelGGL(k_assoc_set_u, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, s, S, p, c, Linv, col_d.p, nent, Ub.p);
+        hipLaunchKernelGGL(k_assoc_set_u, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, s, S, p, c, scan.Linv, col_d.p, nent, Ub.p);
         MIH_TRY(launch_failed("k_assoc_set_u"));
     }
-    const SpaMat mt = assoc_spa_mat(h);
+    const ColView mt = col_view(h);
     PassRecord pr;
     bool timed = prof_begin(h, s, pr);
-#define MIH_SETS_GRAM(KIND) hipLaunchKernelGGL(k_assoc_set_gram<KIND>, dim3((unsigned)ns), dim3(256), 0, s, mt, n, ptr_d.p, col_d.p, om_d.p, V, w, \
-                                               koff_d.p, mused_d.p, mlist_d.p, Kb.p)
-    if (h->kind == 0) MIH_SETS_GRAM(3);
-    else if (h->Du) MIH_SETS_GRAM(2);
-    else if (h->Df) MIH_SETS_GRAM(1);
-    else MIH_SETS_GRAM(0);
-#undef MIH_SETS_GRAM
+    by_kind(h, [&](auto K) {
+        hipLaunchKernelGGL(k_assoc_set_gram<decltype(K)::value>, dim3((unsigned)ns), dim3(256), 0, s, mt, n, ptr_d.p, col_d.p, om_d.p, V, scan.w,
+                           koff_d.p, mused_d.p, mlist_d.p, Kb.p);
+    });
     if (timed) { snprintf(pr.kernel, sizeof(pr.kernel), "k_assoc_set_gram"); pr.residuals = 1; pr.operands = 1; prof_end(h, s, pr); }
     MIH_TRY(launch_failed("k_assoc_set_gram"));
     hipLaunchKernelGGL(k_assoc_set_k, dim3((unsigned)ns), dim3(256), 0, s, ptr_d.p, col_d.p, om_d.p, S, V, c, Ub.p, koff_d.p, mused_d.p, mlist_d.p,
@@ -467,6 +467,20 @@ int assoc_sets_run(const mih_mat *h, hipStream_t s, int c, const double *S, cons
         }
     }
     return MIH_OK;
+}
+
+void sets_publish(const SetsCall &call, const SetsOut &out)
+{
+    if (call.nsets <= 0) return;
+    const size_t ns = (size_t)call.nsets;
+    memcpy(call.m_used, out.m_used.data(), sizeof(int32_t) * ns);
+    memcpy(call.burden_z, out.burden_z.data(), sizeof(double) * ns);
+    memcpy(call.neglog10p_burden, out.nlp_burden.data(), sizeof(double) * ns);
+    memcpy(call.skat_q, out.skat_q.data(), sizeof(double) * ns);
+    memcpy(call.neglog10p_skat, out.nlp_skat.data(), sizeof(double) * ns);
+    memcpy(call.skat_state, out.state.data(), ns);
+    if (call.lambda && !out.lambda.empty()) memcpy(call.lambda, out.lambda.data(), sizeof(double) * out.lambda.size());
+    if (call.cov && !out.cov.empty()) memcpy(call.cov, out.cov.data(), sizeof(double) * out.cov.size());
 }
 
 }  // namespace mih

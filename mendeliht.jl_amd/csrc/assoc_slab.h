@@ -3,21 +3,15 @@
 // ONCE per flagged column (decode by handle kind, the missing list, Z alpha, M1 and the ends of the range), the fixed LDS tree of
 // the 256 partial sums, and the pass over the rows that gives K and K'' at a root.  One copy, inlined into both kernels.
 #pragma once
-#include "grm.h"
+#include "assoc.h"
 
 namespace mih {
-
-struct SpaMat {
-    const double *D; const float *Df; DosageView dv;
-    const uint32_t *X; int64_t nbp; const double *mu, *sinv; int center, scale, impute;
-    const int64_t *miss_ptr; const int32_t *miss_row;
-};
 
 // The pieces of the per-kind column decode that every kernel working on decoded columns shares (the slabs below, the set Gram
 // of assoc_sets.hip).  2-bit: the four values of a column as k_xtv_finalize multiplies them (k_ib_solve's expressions) -- codes
 // 0, 1, 2 and a row of the column's missing list (the list holds a column's rows in ascending order, as the constructors write it).
 struct SnpVals { double x0, x1, x2, xm; };
-__device__ __forceinline__ SnpVals snp_vals(const SpaMat &m, int64_t j)
+__device__ __forceinline__ SnpVals snp_vals(const ColView &m, int64_t j)
 {
 #pragma clang fp contract(off)
     const double s = m.scale ? m.sinv[j] : 1.0, cm = m.center ? m.mu[j] : 0.0;
@@ -27,7 +21,7 @@ __device__ __forceinline__ SnpVals snp_vals(const SpaMat &m, int64_t j)
 }
 // dense f64 (KIND 0), dense f32 (1) and 16-bit dosage (2): the entry mih_xtv multiplies
 template <int KIND>
-__device__ __forceinline__ double slab_dense_x(const SpaMat &m, int64_t n, int64_t j, int64_t i)
+__device__ __forceinline__ double slab_dense_x(const ColView &m, int64_t n, int64_t j, int64_t i)
 {
     return KIND == 0 ? m.D[j * n + i] : KIND == 1 ? (double)m.Df[j * n + i] : dosage_x(m.dv, j, i);
 }
@@ -82,7 +76,7 @@ __device__ __forceinline__ void spa_pass(const double *cs, const double *__restr
 // sum max(c_i, 0) (a2) over its rows tid, tid + 256, ...  al: the column's alpha in LDS, written by the caller before the call
 // (the barriers in here order it).  KIND 0: f64, 1: f32, 2: dosage, 3: 2-bit.
 template <int KIND>
-__device__ __forceinline__ void spa_slab_form(const SpaMat &m, int64_t n, int64_t j, int c, const double *al, const double *__restrict__ Z,
+__device__ __forceinline__ void spa_slab_form(const ColView &m, int64_t n, int64_t j, int c, const double *al, const double *__restrict__ Z,
                                               const double *__restrict__ mu, double *cs, double &a0, double &a1, double &a2)
 {
 #pragma clang fp contract(off)

@@ -23,7 +23,8 @@
 //
 // The slab's formation, the tree and the pass over the rows live in assoc_slab.h, one copy for this kernel and k_assoc_firth;
 // the selection, alpha and the slabs (assoc_flag_run) serve both passes of a call that asks for both.
-#include "assoc_spa.h"
+#include "assoc_slab.h"
+#include "spa_finish.h"
 #include <cmath>
 #include <limits>
 #include <vector>
@@ -93,7 +94,7 @@ k_assoc_spa_alpha(const double *__restrict__ S, int64_t p, int c, const double *
 // status and evaluations of tail 0, of tail 1 (SpaTail).  slab: gridDim.x x n doubles.
 template <int KIND>      // 0: f64, 1: f32, 2: dosage, 3: 2-bit
 __global__ void __launch_bounds__(256)
-k_assoc_spa(SpaMat m, int64_t n, int64_t p, int c, const int64_t *__restrict__ idx, int64_t nflag, const double *__restrict__ alpha,
+k_assoc_spa(ColView m, int64_t n, int64_t p, int c, const int64_t *__restrict__ idx, int64_t nflag, const double *__restrict__ alpha,
             const double *__restrict__ Z, const double *__restrict__ eta, const double *__restrict__ mu, const double *__restrict__ sp0,
             const double *__restrict__ S, const double *__restrict__ V, double *__restrict__ slab, double *__restrict__ rec,
             int32_t *__restrict__ st)
@@ -167,13 +168,14 @@ double assoc_spa_bytes(int64_t n, int64_t p, int c)
     return assoc_flag_bytes(n, p, c) + (double)p * (64.0 + 16.0);   // the tails' values and their status words, had every column been flagged
 }
 
-int assoc_flag_run(const char *who, const mih_mat *h, hipStream_t s, int c, const double *S, const double *z, const double *Linv,
-                   const double *eta_host, double cutoff, AssocFlagged &fl)
+int assoc_flag_run(const char *who, const AssocScan &sc, const double *eta_host, double cutoff, AssocFlagged &fl)
 {
-    const int64_t n = h->n, p = h->p;
+    hipStream_t s = sc.s;
+    const int c = sc.c;
+    const int64_t n = sc.h->n, p = sc.h->p;
     fl.nflag = 0; fl.grid = 0;
     MIH_TRY(fl.idx.alloc((size_t)p + 1));
-    hipLaunchKernelGGL(k_assoc_spa_select, dim3(1), dim3(256), 0, s, z, p, cutoff, fl.idx.p);
+    hipLaunchKernelGGL(k_assoc_spa_select, dim3(1), dim3(256), 0, s, sc.z, p, cutoff, fl.idx.p);
     MIH_TRY(launch_failed("k_assoc_spa_select"));
     int64_t nflag = 0;
     MIH_HIP(hipMemcpyAsync(&nflag, fl.idx.p + p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -187,7 +189,7 @@ int assoc_flag_run(const char *who, const mih_mat *h, hipStream_t s, int c, cons
     MIH_HIP(hipMemcpyAsync(fl.eta.p, eta_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_assoc_spa_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fl.eta.p, n, fl.mu.p, fl.sp0.p);
     MIH_TRY(launch_failed("k_assoc_spa_rows"));
-    hipLaunchKernelGGL(k_assoc_spa_alpha, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, s, S, p, c, Linv, fl.idx.p, nflag, fl.alpha.p);
+    hipLaunchKernelGGL(k_assoc_spa_alpha, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, s, sc.S, p, c, sc.Linv, fl.idx.p, nflag, fl.alpha.p);
     MIH_TRY(launch_failed("k_assoc_spa_alpha"));
     fl.hidx.resize((size_t)nflag);
     MIH_HIP(hipMemcpyAsync(fl.hidx.data(), fl.idx.p, sizeof(int64_t) * (size_t)nflag, hipMemcpyDeviceToHost, s));
@@ -198,41 +200,21 @@ int assoc_flag_run(const char *who, const mih_mat *h, hipStream_t s, int c, cons
     return MIH_OK;
 }
 
-SpaMat assoc_spa_mat(const mih_mat *h)
+int assoc_spa_run(const AssocScan &sc, const AssocFlagged &fl, SpaOut &out)
 {
-    return SpaMat{h->D, h->Df, dosage_view(h), h->X, h->nbp, h->mu, h->sinv, h->center, h->scale, h->impute, h->miss_ptr, h->miss_row};
-}
-
-int assoc_spa_run(const mih_mat *h, hipStream_t s, int c, const AssocFlagged &fl, const double *S, const double *V, const double *Z,
-                  const double *nlp, std::vector<double> &out, std::vector<uint8_t> &state, std::vector<double> &that)
-{
-    const int64_t n = h->n, p = h->p, nflag = fl.nflag, grid = fl.grid;
-    out.assign(nlp, nlp + p);
-    state.assign((size_t)p, 0);
+    const mih_mat *h = sc.h;
+    hipStream_t s = sc.s;
+    const int64_t p = h->p, nflag = fl.nflag;
+    const double *nlp = sc.nlp;
+    std::vector<double> &that = out.t_hat;
+    out.nlp.assign(nlp, nlp + p);
+    out.state.assign((size_t)p, 0);
     that.assign((size_t)(2 * p), std::numeric_limits<double>::quiet_NaN());
     if (nflag == 0) return MIH_OK;
 
-    DevBuf<double> rec;
-    DevBuf<int32_t> st;
-    MIH_TRY(rec.alloc((size_t)(8 * nflag))); MIH_TRY(st.alloc((size_t)(4 * nflag)));
-    SpaMat m = assoc_spa_mat(h);
-    PassRecord pr;
-    const bool timed = prof_begin(h, s, pr);
-#define MIH_SPA_LAUNCH(KIND) hipLaunchKernelGGL(k_assoc_spa<KIND>, dim3((unsigned)grid), dim3(256), 0, s, m, n, p, c, fl.idx.p, nflag, fl.alpha.p, Z, \
-                                                fl.eta.p, fl.mu.p, fl.sp0.p, S, V, fl.slab.p, rec.p, st.p)
-    if (h->kind == 0) MIH_SPA_LAUNCH(3);
-    else if (h->Du) MIH_SPA_LAUNCH(2);
-    else if (h->Df) MIH_SPA_LAUNCH(1);
-    else MIH_SPA_LAUNCH(0);
-#undef MIH_SPA_LAUNCH
-    if (timed) { snprintf(pr.kernel, sizeof(pr.kernel), "k_assoc_spa"); pr.residuals = 1; pr.operands = (int)std::min<int64_t>(nflag, 2147483647); prof_end(h, s, pr); }
-    MIH_TRY(launch_failed("k_assoc_spa"));
-
-    std::vector<double> hrec((size_t)(8 * nflag));
-    std::vector<int32_t> hst((size_t)(4 * nflag));
-    MIH_HIP(hipMemcpyAsync(hrec.data(), rec.p, sizeof(double) * hrec.size(), hipMemcpyDeviceToHost, s));
-    MIH_HIP(hipMemcpyAsync(hst.data(), st.p, sizeof(int32_t) * hst.size(), hipMemcpyDeviceToHost, s));
-    MIH_HIP(hipStreamSynchronize(s));
+    std::vector<double> hrec;
+    std::vector<int32_t> hst;
+    MIH_TRY(assoc_solver_launch(sc, fl, "k_assoc_spa", 8, 4, [](auto K) { return k_assoc_spa<decltype(K)::value>; }, hrec, hst));
 
     int64_t tails = 0, evals = 0;
     for (int64_t f = 0; f < nflag; ++f) {
@@ -246,8 +228,8 @@ int assoc_spa_run(const mih_mat *h, hipStream_t s, int c, const AssocFlagged &fl
             that[(size_t)(k * p + j)] = tl[k].status == 1 ? tl[k].t : std::numeric_limits<double>::quiet_NaN();
         }
         double val = 0.0;
-        state[(size_t)j] = (uint8_t)spa_column(tl, r[0], r[1], nlp[j], &val);
-        out[(size_t)j] = val;
+        out.state[(size_t)j] = (uint8_t)spa_column(tl, r[0], r[1], nlp[j], &val);
+        out.nlp[(size_t)j] = val;
     }
     // a record without a kernel for the measurement hook: the tails computed and the evaluations they took
     PassRecord er;
@@ -257,6 +239,13 @@ int assoc_spa_run(const mih_mat *h, hipStream_t s, int c, const AssocFlagged &fl
         prof_end(h, s, er);
     }
     return MIH_OK;
+}
+
+void spa_publish(const SpaCall &call, const SpaOut &out)
+{
+    memcpy(call.neglog10p_spa, out.nlp.data(), sizeof(double) * out.nlp.size());
+    memcpy(call.state, out.state.data(), out.state.size());
+    if (call.t_hat) memcpy(call.t_hat, out.t_hat.data(), sizeof(double) * out.t_hat.size());
 }
 
 }  // namespace mih
