@@ -582,7 +582,9 @@ int mih_xv_sparse(const mih_mat *h, const int64_t *idx, const double *val, int64
 /* project_k!(x, k) src/utilities.jl:553-559: zero every |x_i| < |k-th largest|;
  * ties at the threshold are kept; *n_kept = number of non-zeros left. */
 int mih_project_topk(double *x, int64_t len, int64_t k, int64_t *n_kept);
-/* project_group_sparse!(y, group, J, k) src/utilities.jl:613-679; group labels 1..G. */
+/* project_group_sparse!(y, group, J, k) src/utilities.jl:613-679; group labels 1..G, G = the largest
+ * label in group.  k points to one entry, or, when k_is_vector, to at least G entries (k[g-1] for label
+ * g; the call reads all G of them and nothing beyond, so a shorter buffer is the caller's error). */
 int mih_project_group_sparse(double *y, const int64_t *group, int64_t len, int64_t J,
                              const int64_t *k, int k_is_vector);
 

@@ -1251,6 +1251,8 @@ def project_group_sparse(y, group, J, k):
     if group.size != y.size:
         raise DimensionMismatch("group must have the length of y")
     kv = np.ascontiguousarray(np.atleast_1d(k), dtype=np.int64)
+    if np.ndim(k) > 0 and group.size and kv.size < group.max():      # the library reads k[0 .. G-1], G = max(group)
+        raise DimensionMismatch("k (vector) must have one entry per group")
     _check(lib().mih_project_group_sparse(_p(y), _p(group), y.size, int(J), _p(kv), int(np.ndim(k) > 0)))
     return y
 

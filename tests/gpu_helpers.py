@@ -880,18 +880,23 @@ def select_constants():
     """The sizes the select's cases are built around, read from csrc/topk.hip and csrc/resident.inc (the cases follow the code); a
     pattern that no longer matches exactly once is an AssertionError naming it."""
     if not _SELECT_CONSTANTS:
-        import re
-        root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mendeliht.jl_amd", "csrc")
-        out = {}
-        for fname, pats in _SELECT_PATTERNS.items():
-            with open(os.path.join(root, fname)) as f:
-                text = f.read()
-            for name, pat in pats.items():
-                found = re.findall(pat, text)
-                assert len(found) == 1, f"{fname}: the pattern of {name} ({pat!r}) matches {len(found)} times, not once"
-                out[name] = int(found[0] or 1)
-        _SELECT_CONSTANTS.update(out)
+        _SELECT_CONSTANTS.update(_constants_from_sources(_SELECT_PATTERNS))
     return dict(_SELECT_CONSTANTS)
+
+
+def _constants_from_sources(patterns):
+    """{name: int} of {file under csrc/: {name: pattern with one group}}; every pattern must match its file exactly once."""
+    import re
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mendeliht.jl_amd", "csrc")
+    out = {}
+    for fname, pats in patterns.items():
+        with open(os.path.join(root, fname)) as f:
+            text = f.read()
+        for name, pat in pats.items():
+            found = re.findall(pat, text)
+            assert len(found) == 1, f"{fname}: the pattern of {name} ({pat!r}) matches {len(found)} times, not once"
+            out[name] = int(found[0] or 1)
+    return out
 
 
 def res_list_of(j, length, mode):
@@ -1528,3 +1533,220 @@ def debias_gram_problem(kind, n, k, flags, seed):
         data = rng.standard_normal((n, p)) * np.exp(rng.uniform(-2, 2, p))
         data = np.asfortranarray(data.astype(np.float32) if kind == "f32" else data)
     return data, debias_support(p, k, rng, ordered=False), rng.standard_normal(n) * 2.0 + 0.5
+
+
+# ---- project_group_sparse! at its edges (csrc/group.hip): the radix sorts' constants read from the source, the inputs, a fit ----
+_GROUP_PATTERNS = {
+    "group.hip": {
+        "items": r"constexpr int kRsItems = (\d+), kRsTile = \d+ \* kRsItems;",
+        "round": r"constexpr int kRsItems = \d+, kRsTile = (\d+) \* kRsItems;",
+        "scan_chunk": r"for \(int64_t base = 0; base < count; base \+= (\d+)\) \{",
+        "scan_threads": r"hipLaunchKernelGGL\(k_rs_scan, dim3\(1\), dim3\((\d+)\), 0, s, hist, \(int64_t\)\d+ \* nblk\);",
+        "digits": r"hipLaunchKernelGGL\(k_rs_scan, dim3\(1\), dim3\(\d+\), 0, s, hist, \(int64_t\)(\d+) \* nblk\);",
+        "key_bits": r"radix_sort_pairs<uint64_t>\(key\.p, key2\.p, idx\.p, perm\.p, len, (\d+), 1, hist\.p, s\);",
+        "label_bits": r"radix_sort_pairs<uint32_t>\(lab\.p, lab2\.p, member\.p, member2\.p, len, (\d+), 0, hist\.p, s\);",
+        "norm_bits": r"radix_sort_pairs<uint64_t>\(nkey\.p, nkey2\.p, gid\.p, gid2\.p, G, (\d+), 1, hist\.p, s\);",
+    },
+}
+_GROUP_CONSTANTS = {}
+
+
+def group_constants():
+    """The sizes of csrc/group.hip's radix sort the group cases are built around, read from the source as select_constants() reads
+    the select's: items (keys a thread owns), round (keys a block takes a round), tile = round x items (keys a block owns),
+    scan_chunk (histogram entries k_rs_scan takes at a time), digits (histogram entries a block contributes), the bits of the
+    three sorts.  A pattern that no longer matches exactly once is an AssertionError naming it."""
+    if not _GROUP_CONSTANTS:
+        _GROUP_CONSTANTS.update(_constants_from_sources(_GROUP_PATTERNS))
+        _GROUP_CONSTANTS["tile"] = _GROUP_CONSTANTS["round"] * _GROUP_CONSTANTS["items"]
+    return dict(_GROUP_CONSTANTS)
+
+
+def group_lengths():
+    T = group_constants()["tile"]
+    return (1, 2, 63, 64, 65, 255, 256, 257, T - 1, T, T + 1, 2 * T, 2 * T + 1, 4 * T, 4 * T + 1, 5 * T + 1)
+
+
+GROUP_LABELS_BYTE2 = (1, 2, 255, 256, 257, 65535, 65536, 65537)       # and G - 1, G
+GROUP_G_BYTE2, GROUP_G_BYTE3 = 70001, 2 ** 24 + 3
+GROUP_VALUE_KINDS = ("equal", "zeros", "extremes", "onebyte", "normal")
+_GROUP_COMBOS = ((1, 1, 3), (3, 2, 1), (300, 150, 3), (3, 2, "vec"), (300, 150, "vec"))       # (G, J, k)
+_GROUP_CASES, _GROUP_KNOWN = [], {}
+
+
+def group_values(kind, rng, n):
+    """n values of one kind: "equal" -- one |y|, random signs (index order alone decides); "zeros" -- 0.0, -0.0, +-1; "extremes" --
+    denormals, the smallest normal, 1e-200, 1e308, +-Inf; "onebyte" -- |y| with the bit pattern 1 << j, j uniform in 0 .. 62 (two
+    keys differ in ONE byte or in two: every pass of the key sort is the only one that orders some pair); "normal" -- N(0, 1)."""
+    sign = rng.choice([-1.0, 1.0], n)
+    if kind == "equal":
+        return 1.5 * sign
+    if kind == "zeros":
+        return rng.choice(np.array([0.0, -0.0, 1.0, -1.0]), n)
+    if kind == "extremes":
+        return rng.choice(np.array([5e-324, -1e-323, 2.2250738585072014e-308, 1e-200, 1e308, np.inf, -np.inf]), n)
+    if kind == "onebyte":
+        v = (np.uint64(1) << rng.integers(0, 63, n).astype(np.uint64)).view(np.float64).copy()
+        v[np.isnan(v)] = 1.0
+        return v * sign
+    assert kind == "normal"
+    return rng.standard_normal(n)
+
+
+def group_edge_cases():
+    """THE inputs of tests/test_gpu_group_edges.py and of its CPU companion tests/test_group_spec_cpu.py (which shows that every
+    case has the property its name promises): a list of (name, y, group, J, k), k an int or an int64 vector.  No NaN anywhere.
+    T = tile; the lengths 1 .. 5 T + 1 of group_lengths(): a partial wave, a partial round, a last tile of one key, a histogram of
+    exactly one scan chunk (4 T) and the first whose carry matters (4 T + 1)."""
+    if _GROUP_CASES:
+        return list(_GROUP_CASES)
+    T = group_constants()["tile"]
+    L = group_lengths()
+    out, names = [], set()
+
+    def rng_of(tag):
+        return np.random.default_rng([20290, *[ord(c) for c in tag]])
+
+    def add(name, y, group, J, k):
+        assert name not in names, name
+        names.add(name)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        group = np.ascontiguousarray(group, dtype=np.int64)
+        assert y.ndim == 1 and y.shape == group.shape and not np.isnan(y).any()
+        out.append((name, y, group, int(J), int(k) if np.ndim(k) == 0 else np.ascontiguousarray(k, dtype=np.int64)))
+
+    def kvec(rng, G, group):
+        k = rng.integers(0, 4, G)
+        k[int(group[0]) - 1] = 0                            # a 0 at a populated label
+        if group.size > 1 and group[-1] != group[0]:
+            k[int(group[-1]) - 1] = 3
+        return k
+
+    # (a) the value kinds across the lengths: every length for the stability kind and the control, every combination of (G, J, k)
+    # from the first tile edge on for the stability kind, two of them (dealt round) elsewhere
+    per_kind = {"equal": L, "normal": L,
+                "zeros": (1, 2, 65, 257, T, T + 1, 2 * T + 1, 4 * T + 1),
+                "extremes": (2, 64, 256, T - 1, T + 1, 4 * T + 1),
+                "onebyte": (255, 257, T, T + 1, 2 * T, 4 * T + 1, 5 * T + 1)}
+    for kind in GROUP_VALUE_KINDS:
+        for t, n in enumerate(per_kind[kind]):
+            every = kind == "equal" and n >= T - 1
+            for c in range(len(_GROUP_COMBOS)) if every else ((2 * t) % 5, (2 * t + 1) % 5):
+                G, J, k = _GROUP_COMBOS[c]
+                rng = rng_of(f"{kind}{n}c{c}")
+                group = rng.integers(1, G + 1, n)
+                add(f"{kind} len={n} G={G} J={J} k={k}", group_values(kind, rng, n), group, J, kvec(rng, G, group) if k == "vec" else k)
+    # a kept -0.0 stays -0.0: everything kept
+    for n in (257, T + 1):
+        rng = rng_of(f"keepall{n}")
+        add(f"zeros len={n} everything kept", group_values("zeros", rng, n), rng.integers(1, 4, n), 3, 2 ** 62)
+
+    # (b) label layouts
+    for n in (300, 2 * T + 1):
+        rng = rng_of(f"layout{n}")
+        y = rng.standard_normal(n)
+        add(f"one group len={n}", y, np.ones(n), 1, 3)
+        for J in (1, 299, 300):
+            add(f"every entry labelled 300 len={n} J={J}", y, np.full(n, 300), J, 3)
+        add(f"labels 1 and 300 only len={n}", y, rng.choice([1, 300], n), 2, 3)
+        add(f"labels 1 and 300 only len={n} vector k", y, rng.choice([1, 300], n), 2, np.r_[2, rng.integers(0, 4, 298), 3])
+        mid = rng.choice(np.r_[1:101, 201:301], n)
+        add(f"labels 101..200 empty len={n} J=150", y, mid, 150, 1)
+        add(f"labels 101..200 empty len={n} J=250 vector k", y, mid, 250, kvec(rng, 300, mid))
+    for tag, G in (("byte 2", GROUP_G_BYTE2), ("byte 3", GROUP_G_BYTE3)):
+        rng = rng_of(tag)
+        pool = np.array(GROUP_LABELS_BYTE2 + ((2 ** 24, 2 ** 24 + 1) if G == GROUP_G_BYTE3 else ()) + (G - 1, G))
+        group = np.r_[pool, rng.choice(pool, 300 - pool.size)][rng.permutation(300)]
+        y = rng.standard_normal(300)
+        if G == GROUP_G_BYTE3:
+            add(f"label {tag}: G={G} len=300 J=5 k=3", y, group, 5, 3)
+            continue
+        for J in (1, 5, G):
+            add(f"label {tag}: G={G} len=300 J={J} k=3", y, group, J, 3)
+        add(f"label {tag}: G={G} len=300 J=6 vector k", y, group, 6, kvec(rng, G, group))
+        add(f"label {tag}: G={G} len=300 equal |y| J=4 k=2", group_values("equal", rng, 300), group, 4, 2)
+
+    # (c) degenerate J and k
+    for n, G in ((257, 3), (T + 1, 300)):
+        rng = rng_of(f"degenerate{n}")
+        y = rng.standard_normal(n)
+        group = rng.integers(1, G + 1, n)
+        group[:2] = (1, G)
+        for J in (0, 1, G, G + 3, 2 ** 40):
+            add(f"J={J} len={n} G={G} k=3", y, group, J, 3)
+        for k in (0, 1, 3, 2 ** 62):
+            add(f"k={k} len={n} G={G} J=2", y, group, 2, k)
+        kv = kvec(rng, G, group)
+        add(f"vector k with a 0 at a populated label len={n} G={G}", y, group, G, kv)
+        big = kv.copy()
+        big[G - 1] = 2 ** 62
+        add(f"vector k with 2^62 inside len={n} G={G}", y, group, max(G - 1, 1), big)
+        add(f"vector k longer than G len={n} G={G}", y, group, 2, np.r_[kv, rng.integers(0, 4, 7)])
+        add(f"vector k all 0 len={n} G={G}", y, group, 2, np.zeros(G, dtype=np.int64))
+
+    # (d) ties with a known answer
+    big = 2.0 ** 27                                          # big^2 = 2^54, where an ulp is 4: adding 1.0 nine times, one at a time, changes nothing
+    ones = np.array([1.0, -1.0, 1.0, 1.0, -1.0, 1.0, -1.0, -1.0, 1.0])
+    y = np.r_[0.5, ones[:4], -big, -0.25, ones[4:], big, 0.5]
+    for lone, many in ((1, 2), (2, 1)):
+        group = np.r_[3, [many] * 4, many, 3, [many] * 5, lone, 3]
+        want = np.where(group == min(lone, many), y, 0.0)
+        name = f"tie across the cut by the sequential sum, the lone entry is group {lone}"
+        add(name, y, group, 1, 10)
+        _GROUP_KNOWN[name] = want
+    y = np.array([6.0, 3.0, 0.5, -5.0, 1.0, -4.0, 0.25, 0.125])
+    group = np.array([1, 2, 3, 5, 1, 2, 3, 3])
+    for J, alive in ((2, (1, 2)), (3, (1, 2, 5))):
+        name = f"3^2 + 4^2 against 5^2 across the cut J={J}"
+        add(name, y, group, J, 2)
+        _GROUP_KNOWN[name] = np.where(np.isin(group, alive), y, 0.0)      # norms 37, 25, 0.3125, 0 (label 4 is absent), 25
+    y = np.array([-0.0, 1.0, 3.0, 0.0, -2.0, -0.0, -0.0, -0.0])
+    group = np.array([5, 2, 9, 5, 2, 5, 9, 10])
+    k = np.full(10, 2)
+    k[8] = 0
+    k[4] = 3
+    for J, alive in ((4, (2,)), (5, (2, 5)), (8, (2, 5)), (10, (2, 5, 10))):      # the ranking: 2, then the zero norms by label: 1, 3, 4, 5, 6, 7, 8, 9, 10
+        name = f"J beyond the non-empty groups: zero norms rank by label J={J}"
+        add(name, y, group, J, k)
+        _GROUP_KNOWN[name] = np.where(np.isin(group, alive), y, 0.0)
+    _GROUP_CASES.extend(out)
+    return list(out)
+
+
+def group_known_answers():
+    """{name: the projection written down by hand} of the tie cases of group_edge_cases()."""
+    group_edge_cases()
+    return dict(_GROUP_KNOWN)
+
+
+GROUP_FIT_N, GROUP_FIT_P, GROUP_FIT_G, GROUP_FIT_SEED = 301, 4101, 41, 613
+GROUP_FIT_CAUSAL = (5, 22, 41)
+_GROUP_FIT = {}
+
+
+def group_fit_problem():
+    """The fit of tests/test_gpu_group_edges.py: 301 x 4101 genotypes (make_bed, seed 613, maf >= 0.05) -- the projection sorts
+    4101 keys: two full tiles and a third -- with interleaved labels 1 + (7 j mod 41), label 13 relabelled 14 (absent), two causal
+    SNPs in each of the groups 5, 22 and 41 with effects +-U(0.6, 0.9), an intercept and one Gaussian covariate.  Returns
+    dict(cols, z, group, causal, y={"normal": ..., "bernoulli": ...}, settings=[(k, J), ...])."""
+    if _GROUP_FIT:
+        return dict(_GROUP_FIT)
+    from conftest import make_bed
+    n, p, G = GROUP_FIT_N, GROUP_FIT_P, GROUP_FIT_G
+    rng = np.random.default_rng(GROUP_FIT_SEED)
+    cols = make_bed(rng, n, p, maf_lo=0.05)
+    group = 1 + (np.arange(p) * 7 % G)
+    group[group == 13] = 14
+    causal = np.sort(np.concatenate([rng.choice(np.flatnonzero(group == g), 2, replace=False) for g in GROUP_FIT_CAUSAL]))
+    beta = np.zeros(p)
+    beta[causal] = rng.choice([-1.0, 1.0], causal.size) * rng.uniform(0.6, 0.9, causal.size)
+    g = _dosages(cols[causal], n).astype(np.float64)
+    eta = beta[causal] @ ((g - g.mean(axis=1, keepdims=True)) / g.std(axis=1, keepdims=True))
+    z = np.column_stack([np.ones(n), rng.standard_normal(n)])
+    y_normal = eta + 0.7 + 0.4 * z[:, 1] + rng.standard_normal(n)
+    y_bern = (rng.random(n) < 1.0 / (1.0 + np.exp(-(1.5 * eta + 0.2)))).astype(np.float64)
+    kv = np.ones(G, dtype=np.int64)
+    kv[np.array(GROUP_FIT_CAUSAL) - 1] = 2
+    kv[13 - 1] = 0
+    _GROUP_FIT.update(cols=cols, z=z, group=group, causal=causal, y={"normal": y_normal, "bernoulli": y_bern}, settings=[(2, 3), (kv, 4)])
+    return dict(_GROUP_FIT)
