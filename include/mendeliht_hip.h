@@ -481,7 +481,7 @@ int mih_assoc_score_firth(const mih_mat *h, const double *A /* n: y - mu */, con
  * burden_z, neglog10p_burden, skat_q, neglog10p_skat or skat_state, nsets < 0, a null set_ptr, a set_ptr that does not start at 0 or
  * decreases, a set of more than 128 entries, null set_col or omega with entries, a column outside [0, p), columns of a set not
  * strictly ascending, an omega that is negative or not finite.  nsets = 0 is valid and returns the scan alone.
- * Not offered: SKAT-O, ACAT, saddlepoint-adjusted variances for unbalanced case-control sets, collapsing of ultra-rare variants,
+ * Not offered: ACAT, saddlepoint-adjusted variances for unbalanced case-control sets, collapsing of ultra-rare variants,
  * sets of more than 128 entries. */
 int mih_assoc_sets(const mih_mat *h, const double *A /* n */, const double *w /* n, or NULL */, const double *Z /* n x c */, int32_t c,
                    int64_t slice_rows, int32_t nsets, const int64_t *set_ptr /* nsets + 1 */, const int32_t *set_col, const double *omega,
@@ -489,6 +489,63 @@ int mih_assoc_sets(const mih_mat *h, const double *A /* n */, const double *w /*
                    int32_t *m_used /* nsets */, double *burden_z /* nsets */, double *neglog10p_burden /* nsets */,
                    double *skat_q /* nsets */, double *neglog10p_skat /* nsets */, uint8_t *skat_state /* nsets */,
                    double *lambda /* like set_col, may be NULL */, double *cov /* sum m_s^2, may be NULL */);
+/* mih_assoc_sets with SKAT-O on top: the optimal combination of the burden and the SKAT test of every set (Lee, Wu and Lin 2012;
+ * csrc/assoc_skato.hip, csrc/skato_tail.h; tests/skato_spec.py states the same in numpy).  Every argument and output of
+ * mih_assoc_sets keeps its meaning and its bits.  The grid: nrho values rho_1 < ... < rho_R in [0, 1], 1 <= nrho <= 16;
+ * rho = NULL is SKAT's optimal.adj grid 0, 0.01, 0.04, 0.09, 0.16, 0.25, 0.5, 1 and needs nrho = 8.  A value above 0.999 is used as
+ * 0.999, as SKAT does.
+ * Per set with m members, M, rs_j = sum_k M_jk, S, T, Q as above, and per rho:
+ *   Q_rho = (1 - rho) Q + rho (T T)
+ *   M_rho = R_rho^1/2 M R_rho^1/2, R_rho = (1 - rho) I + rho 11', formed without a factorisation: c = sqrt(1 - rho),
+ *           d = (sqrt((1 - rho) + m rho) - c) / m,  M_rho[j, k] = ((c c) M_jk + (c d) (rs_j + rs_k)) + (d d) S for j >= k, mirrored.  At
+ *           rho = 0, c = 1 and d = 0 exactly: M_0 is M and its eigenvalues are `lambda` bit for bit (the same Jacobi code).
+ *   lambda^(rho): the eigenvalues of M_rho, descending, every value <= 0 set to 0;  p_rho: the saddlepoint tail of
+ *           (lambda^(rho), Q_rho) with the states of skat_state -- neglog10p_rho, and at rho = 0 neglog10p_skat bit for bit
+ *   p_min = min_rho p_rho;  skato_rho = its rho as the caller gave it (a tie goes to the smaller rho)
+ *   q_rho: tail_rho(q_rho) = p_min.  For skato_rho it is Q_rho.  For a rank-one lambda^(rho) it is lambda_1 z^2, z the two-sided
+ *           normal quantile of p_min (bisection on neglog10p_of_z).  Otherwise the saddlepoint is inverted in its own parameter
+ *           s = 2 lambda_1 t: q = lambda_1 g(s), log tail = log Phi(-r(s)); in y = 1 / (1 - s), F(y) = log tail - log p_min:
+ *           a = 1 / (1 - s_rho) (the saddlepoint of Q_rho); |F(a)| <= 2^-40 |log p_min| or F(a) < 0: take a.  b = 2 a; while F(b) > 0:
+ *           a = b, b = 2 b.  Then the Illinois rule: y = b - F(b) (b - a) / (F(b) - F(a)), the midpoint if that is not inside (a, b);
+ *           |F(y)| <= 2^-40 |log p_min|: converged; F(y) > 0: a = y, and F(b) is halved if a moved the last time too; else b = y, and
+ *           F(a) is halved likewise; b - a <= 2^-40 b: converged too, with this y.  128 evaluations of F in all: not converged.
+ *   M~ = M - rs rs' / S (entry j >= k: M_jk - (rs_j rs_k) / S, mirrored), lambda~ its eigenvalues (values <= 0 set to 0);
+ *   mu = sum lambda~,  v_xi = 4 (rs' M~ rs) / S (not below 0),  v = 2 sum lambda~^2 + v_xi,  tau_rho = rho S + (1 - rho) (rs' rs) / S
+ *   delta(x) = min_rho (q_rho - tau_rho x) / (1 - rho),  delta'(x) = (delta(x) - mu) sqrt((v - v_xi) / v) + mu,  u0^2 = min_rho q_rho / tau_rho
+ *   p = 2 int_0^u0 S~(delta'(u^2)) phi(u) du + 2 Phi(-u0),  S~ the saddlepoint tail of lambda~, 1 where delta' <= 0.  (x = u^2 removes
+ *           the singularity of the chi2_1 density; beyond u0 the integrand is that density exactly, so nothing is truncated.)
+ *   The integral: 16 panels of [0, u0], the 16-point Gauss-Legendre rule in each, one node per thread; every term a logarithm
+ *           (log weight + log S~ + log phi + log(h / 2), h the panel's width), combined by a fixed pairwise log-sum-exp tree.  delta
+ *           has up to R - 1 kinks where the minimising rho changes; the panels are cut there.  The kinks: with
+ *           a_rho = q_rho / (1 - rho), b_rho = tau_rho / (1 - rho), a walk along the lower envelope of the lines a - b x from the line
+ *           lowest at x = 0 (the steepest among equals); the next kink is the nearest crossing ahead with a steeper line (the
+ *           steepest among equals), until u0^2.  The panels: the segments between 0, the kinks (as u = sqrt x) and u0 get one panel
+ *           each, the remaining ones go one at a time to the segment whose panels are widest (the first among equals); a
+ *           segment's panels are equal.  The device's libm is not the host's: the value agrees with tests/skato_spec.py to a
+ *           tolerance, and is the same bits for every slice_rows, position of the set and list of other sets.
+ * skato_state and neglog10p_skato:
+ *   0  no value: m = 0, S <= 0 (or NaN), skat_state 0, or a p_rho without a value: NaN
+ *   2  rank one: m = 1 or skat_state 2: neglog10p_skat bit for bit (skato_rho is NaN)
+ *   4  fallback: a p_rho came from state 4 or 5, p_min = 1, a quantile did not converge or the integral is not a number:
+ *      min(1, R p_min)
+ *   1  the integral's value
+ *   3  clamped: the integral left [p_min, R p_min] and was moved to the nearer end (SKAT's own rule)
+ * neglog10p_rho (nsets x nrho, row-major, may be NULL).  lambda_rho (may be NULL): nrho + 1 arrays laid out like set_col, one after
+ * the other: lambda^(rho_1) .. lambda^(rho_R), then lambda~; NaN after m_used.
+ * Memory: beside mih_assoc_sets's, nrho + 1 Jacobi slabs for every set of more than 64 entries, lambda_rho and the integrands, all
+ * counted in the same check before anything is allocated.
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: everything mih_assoc_sets refuses, a null neglog10p_skato,
+ * skato_rho or skato_state, nrho < 1 or > 16, rho = NULL with nrho != 8, a rho outside [0, 1] (or NaN), a grid not strictly
+ * ascending. */
+int mih_assoc_sets_skato(const mih_mat *h, const double *A /* n */, const double *w /* n, or NULL */, const double *Z /* n x c */, int32_t c,
+                         int64_t slice_rows, int32_t nsets, const int64_t *set_ptr /* nsets + 1 */, const int32_t *set_col, const double *omega,
+                         int32_t nrho, const double *rho /* nrho, or NULL: the default grid */,
+                         double *z /* p */, double *beta /* p */, double *se /* p */, double *neglog10p /* p */,
+                         int32_t *m_used /* nsets */, double *burden_z /* nsets */, double *neglog10p_burden /* nsets */,
+                         double *skat_q /* nsets */, double *neglog10p_skat /* nsets */, uint8_t *skat_state /* nsets */,
+                         double *lambda /* like set_col, may be NULL */, double *cov /* sum m_s^2, may be NULL */,
+                         double *neglog10p_skato /* nsets */, double *skato_rho /* nsets */, uint8_t *skato_state /* nsets */,
+                         double *neglog10p_rho /* nsets x nrho, may be NULL */, double *lambda_rho /* (nrho + 1) x entries, may be NULL */);
 /* Re-expresses every non-missing numerator of a dosage handle over denom (a multiple of its denominator, at most 32767) and
  * recomputes the column statistics: the same matrix on a finer grid (column shards agree on one denominator this way).  Not
  * while a fit uses the handle. */

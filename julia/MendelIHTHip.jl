@@ -133,6 +133,36 @@ function assoc_sets(x::HipSnpLinAlg{Float64}, A::Vector{Float64}, w::Union{Nothi
             z=z, beta=beta, se=se, neglog10p=nlp)
 end
 
+# The same with SKAT-O on top (mih_assoc_sets_skato): rho = the grid, ascending values in [0, 1], at most 16 (nothing: SKAT's
+# default grid of 8).  neglog10p_rho is nrho x nsets, lambda_rho entries x (nrho + 1) (column-major views of the C layout).
+function assoc_sets_skato(x::HipSnpLinAlg{Float64}, A::Vector{Float64}, w::Union{Nothing, Vector{Float64}}, Z::Matrix{Float64},
+                          sets::Vector{Vector{Int}}; omega::Union{Nothing, Vector{Vector{Float64}}}=nothing,
+                          rho::Union{Nothing, Vector{Float64}}=nothing, slice_rows::Integer=0)
+    ns = length(sets)
+    set_ptr = Int64[0; cumsum(length.(sets))]
+    set_col = Int32[j - 1 for s in sets for j in s]
+    om = omega === nothing ? ones(length(set_col)) : Float64[v for o in omega for v in o]
+    length(om) == length(set_col) || throw(DimensionMismatch("omega has $(length(om)) entries, the sets have $(length(set_col))"))
+    nrho = rho === nothing ? 8 : length(rho)
+    z = zeros(x.p); beta = zeros(x.p); se = zeros(x.p); nlp = zeros(x.p)
+    m_used = zeros(Int32, ns); state = zeros(UInt8, ns)
+    bz = zeros(ns); bn = zeros(ns); sq = zeros(ns); sn = zeros(ns); lam = zeros(length(set_col))
+    so = zeros(ns); sr = zeros(ns); ss = zeros(UInt8, ns); pr = zeros(nrho, ns); lr = zeros(length(set_col), nrho + 1)
+    check(ccall((:mih_assoc_sets_skato, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
+                 Int32, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{UInt8}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}),
+                x.handle, A, w === nothing ? C_NULL : w, Z, size(Z, 2), slice_rows, ns, set_ptr, set_col, om,
+                nrho, rho === nothing ? C_NULL : rho,
+                z, beta, se, nlp, m_used, bz, bn, sq, sn, state, lam, C_NULL,
+                so, sr, ss, pr, lr))
+    return (m_used=m_used, burden_z=bz, neglog10p_burden=bn, skat_q=sq, neglog10p_skat=sn, skat_state=state, lambda=lam,
+            neglog10p_skato=so, skato_rho=sr, skato_state=ss, neglog10p_rho=pr, lambda_rho=lr,
+            z=z, beta=beta, se=se, neglog10p=nlp)
+end
+
 # naive_impute(x, destination) (utilities.jl:862-899) on the device copy of the genotypes
 function naive_impute(x::HipSnpLinAlg{Float64}, destination::String)
     out = Matrix{UInt8}(undef, (x.n + 3) >> 2, x.p)

@@ -176,6 +176,8 @@ _SIGNATURES = {
     "mih_assoc_score_spa": [_vp, _vp, _vp, _vp, _i32, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mih_assoc_score_firth": [_vp, _vp, _vp, _vp, _i32, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mih_assoc_sets": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mih_assoc_sets_skato": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp, _vp],
     "mih_snp_naive_impute": [_vp, _vp],
     "mih_xtv": [_vp, _vp, _vp],
     "mih_xtv_batched": [_vp, _vp, C.c_int, _vp],
@@ -579,14 +581,19 @@ class _Mat:
             raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
         return y, np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
 
-    def set_test(self, A, w, Z, sets, omega=None, slice_rows=0, cov=False):
+    def set_test(self, A, w, Z, sets, omega=None, slice_rows=0, cov=False, skato=False, rho=None):
         """Burden and SKAT tests of sets of columns on top of the score test of every column -- mih_assoc_sets as it is: score
         residuals A (n: one trait), working weights w (None: ones) and covariates Z (None: an intercept) as score_test takes
         them.  sets: a list of index arrays (0-based columns, strictly ascending within a set, at most 128), or the pair
         (set_ptr, set_col); omega: one weight >= 0 per entry, as a list of arrays like sets or one flat array (None: ones).
         Returns a SetResult; cov=True also keeps every set's covariance K of the scores (a list of m_s x m_s arrays over the
-        entries, NaN in the rows and columns of entries that are not members)."""
+        entries, NaN in the rows and columns of entries that are not members).  skato=True adds SKAT-O, the optimal combination
+        of the two tests over the grid rho (ascending values in [0, 1], at most 16; None: SKAT's 0, 0.01, 0.04, 0.09, 0.16, 0.25,
+        0.5, 1) -- mih_assoc_sets_skato as it is: the SetResult then has neglog10p_skato, skato_rho, skato_state, neglog10p_rho
+        and lambda_rho; every other output is the same bits as without it."""
         from .assoc import AssocResult, SetResult
+        if rho is not None and not skato:
+            raise ArgumentError("rho is the grid of SKAT-O: give skato=True with it")
         A, w, Z, _ = _scan_args(self.n, A, w, Z)
         if isinstance(sets, tuple):                     # a tuple is (set_ptr, set_col), a list is a list of sets
             if len(sets) != 2:
@@ -621,15 +628,27 @@ class _Mat:
         lam = np.empty(col.size)
         sizes = np.diff(ptr)
         cv = np.empty(int((sizes * sizes).sum())) if cov else None
-        _check(lib().mih_assoc_sets(self._h, _p(A), _p(w), _p(Z), Z.shape[1], int(slice_rows), ns, _p(ptr), _p(col), _p(om),
-                                    _p(z), _p(beta), _p(se), _p(nlp), _p(m_used), _p(bz), _p(bn), _p(sq), _p(sn), _p(state), _p(lam), _p(cv)))
+        extra = None
+        if skato:
+            grid = None if rho is None else np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+            nr = 8 if grid is None else grid.size
+            if not 1 <= nr <= 16:
+                raise ArgumentError(f"rho must hold 1 to 16 grid values, got {nr}")
+            so = np.empty(k); sr = np.empty(k); ss = np.empty(k, dtype=np.uint8); pr = np.empty((k, nr)); lr = np.empty((nr + 1, col.size))
+            _check(lib().mih_assoc_sets_skato(self._h, _p(A), _p(w), _p(Z), Z.shape[1], int(slice_rows), ns, _p(ptr), _p(col), _p(om), nr, _p(grid),
+                                              _p(z), _p(beta), _p(se), _p(nlp), _p(m_used), _p(bz), _p(bn), _p(sq), _p(sn), _p(state), _p(lam), _p(cv),
+                                              _p(so), _p(sr), _p(ss), _p(pr), _p(lr)))
+            extra = (so, sr, ss, pr, lr)
+        else:
+            _check(lib().mih_assoc_sets(self._h, _p(A), _p(w), _p(Z), Z.shape[1], int(slice_rows), ns, _p(ptr), _p(col), _p(om),
+                                        _p(z), _p(beta), _p(se), _p(nlp), _p(m_used), _p(bz), _p(bn), _p(sq), _p(sn), _p(state), _p(lam), _p(cv)))
         covs = None
         if cov:
             off = np.concatenate([[0], np.cumsum(sizes * sizes)]).astype(np.int64)
             covs = [cv[off[s]:off[s + 1]].reshape(sizes[s], sizes[s]).copy() for s in range(ns)]
-        return SetResult(ptr, col, om, m_used, bz, bn, sq, sn, state, lam, covs, AssocResult(z, beta, se, nlp))
+        return SetResult(ptr, col, om, m_used, bz, bn, sq, sn, state, lam, covs, AssocResult(z, beta, se, nlp), skato=extra)
 
-    def assoc_sets(self, y, z, sets, *, d=None, l=None, weights="beta", beta=(1, 25), max_maf=None, slice_rows=0, cov=False):
+    def assoc_sets(self, y, z, sets, *, d=None, l=None, weights="beta", beta=(1, 25), max_maf=None, slice_rows=0, cov=False, skato=False, rho=None):
         """Gene-based burden and SKAT tests: the null model y ~ z (fit_null, as assoc fits it; z=None: an intercept; a Normal
         trait is scaled by 1 / sqrt(phi) as in assoc) and set_test against it.  weights="beta": omega_j is the Beta(a, b) density
         at the minor allele frequency of column j, beta = (a, b) -- SKAT's default (1, 25) -- divided by sinv_j on a scaled
@@ -638,7 +657,7 @@ class _Mat:
         on the scaled column gives omega_j U_j and omega_j omega_k K_jk: SKAT's weighting of the raw genotypes, whatever the
         flags of the handle.  weights may be an array of p weights instead (used as they are; a DenseMatrix, which has no allele
         frequencies, takes only that).  max_maf: entries whose minor allele frequency is above it (or not a number) are dropped
-        from their sets.  Returns a SetResult whose `assoc.null` is the NullModel."""
+        from their sets.  skato, rho: SKAT-O as set_test offers it.  Returns a SetResult whose `assoc.null` is the NullModel."""
         d = Normal() if d is None else _inst(d)
         y, zc = self._trait_args(y, z, d, "assoc_sets")
         parts = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
@@ -673,7 +692,7 @@ class _Mat:
         null, A, w, rt = _null_scores(y, zc, d, l)
         if rt is not None:
             null, A, rt = null[0], A[:, 0], rt[0]
-        res = self.set_test(A, w, zc, parts, [om[q] for q in parts], slice_rows=slice_rows, cov=cov)
+        res = self.set_test(A, w, zc, parts, [om[q] for q in parts], slice_rows=slice_rows, cov=cov, skato=skato, rho=rho)
         if rt is not None:
             res.assoc.beta, res.assoc.se = res.assoc.beta * rt, res.assoc.se * rt
         res.assoc.null = null
@@ -2074,12 +2093,13 @@ def gwas(plinkfile, d, *, phenotypes=6, covariates="", outfile="gwas.txt", exclu
 
 
 def gwas_sets(plinkfile, d, setfile, *, phenotypes=6, covariates="", outfile="gwas_sets.txt", exclude_std_idx=(), device=0, l=None,
-              weights="beta", beta=(1, 25), max_maf=None, slice_rows=0):
+              weights="beta", beta=(1, 25), max_maf=None, slice_rows=0, skato=False, rho=None):
     """The gene-based tests of a file, beside gwas(): the inputs are parsed as gwas parses them; setfile has two
     whitespace-separated columns `set_id snp_id` (lines starting with # are skipped), the SNP ids are those of the .bim; a set is
     the SNPs of its id in .bim order, in the order the ids first appear.  An id the .bim does not have, and a set of more than
     128 SNPs, are ArgumentErrors naming the first.  x.assoc_sets does the rest.  outfile: `set_id n_snps m_used burden_z
-    neglog10p_burden skat_q neglog10p_skat skat_state`, one row per set, tab-separated.  Returns (set ids, SetResult)."""
+    neglog10p_burden skat_q neglog10p_skat skat_state`, one row per set, tab-separated; skato=True (with the grid rho, as set_test
+    takes it) appends `neglog10p_skato skato_rho skato_state`.  Returns (set ids, SetResult)."""
     d = _inst(d)
     x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, False, device, False)
     if _is_multivariate(y):
@@ -2105,13 +2125,15 @@ def gwas_sets(plinkfile, d, setfile, *, phenotypes=6, covariates="", outfile="gw
     for k, s in zip(ids, sets):
         if s.size > 128:
             raise ArgumentError(f"set {k} has {s.size} SNPs, at most 128 are supported")
-    res = x.assoc_sets(y, z, sets, d=d, l=l, weights=weights, beta=beta, max_maf=max_maf, slice_rows=slice_rows)
+    res = x.assoc_sets(y, z, sets, d=d, l=l, weights=weights, beta=beta, max_maf=max_maf, slice_rows=slice_rows, skato=skato, rho=rho)
     if outfile:
         with open(outfile, "w") as f:
-            f.write("set_id\tn_snps\tm_used\tburden_z\tneglog10p_burden\tskat_q\tneglog10p_skat\tskat_state\n")
+            f.write("set_id\tn_snps\tm_used\tburden_z\tneglog10p_burden\tskat_q\tneglog10p_skat\tskat_state" +
+                    ("\tneglog10p_skato\tskato_rho\tskato_state" if skato else "") + "\n")
             for k, name in enumerate(ids):
+                more = f"\t{float(res.neglog10p_skato[k])!r}\t{float(res.skato_rho[k])!r}\t{int(res.skato_state[k])}" if skato else ""
                 f.write(f"{name}\t{int(res.set_ptr[k + 1] - res.set_ptr[k])}\t{int(res.m_used[k])}\t{float(res.burden_z[k])!r}\t"
-                        f"{float(res.neglog10p_burden[k])!r}\t{float(res.skat_q[k])!r}\t{float(res.neglog10p_skat[k])!r}\t{int(res.skat_state[k])}\n")
+                        f"{float(res.neglog10p_burden[k])!r}\t{float(res.skat_q[k])!r}\t{float(res.neglog10p_skat[k])!r}\t{int(res.skat_state[k])}{more}\n")
     return ids, res
 
 

@@ -181,18 +181,26 @@ class SetResult:
     2 rank one: the exact chi-square tail, 3 at the mean: the limit, 4 Q <= 0: p = 1, 5 the root iteration gave up: the
     moment-matched normal).  set_ptr, set_col, omega: the sets as they went in.  lambdas: the eigenvalues of every set's M, laid
     out like set_col (NaN after m_used); lambdas_of(s) gives one set's.  cov: None, or the list of the sets' covariance matrices.
-    assoc: the AssocResult of the per-column scan of the same call."""
-    def __init__(self, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambdas, cov, assoc):
+    assoc: the AssocResult of the per-column scan of the same call.
+    With skato=True (None otherwise): neglog10p_skato, the SKAT-O p-value; skato_rho, the grid value whose test has the smallest
+    p-value (NaN without one); skato_state (uint8: 0 no value, 1 the integral, 2 rank one: neglog10p_skat itself, 3 the integral
+    clamped to [p_min, R p_min], 4 fallback: min(1, R p_min)); neglog10p_rho (sets x R: the p-value of every grid value) and
+    lambda_rho ((R + 1) x entries: the eigenvalues behind them and, last, those of the remainder M~)."""
+    def __init__(self, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambdas, cov, assoc, skato=None):
         self.set_ptr, self.set_col, self.omega, self.m_used = set_ptr, set_col, omega, m_used
         self.burden_z, self.neglog10p_burden, self.skat_q, self.neglog10p_skat = burden_z, neglog10p_burden, skat_q, neglog10p_skat
         self.skat_state, self.lambdas, self.cov, self.assoc = skat_state, lambdas, cov, assoc
+        self.neglog10p_skato, self.skato_rho, self.skato_state, self.neglog10p_rho, self.lambda_rho = skato if skato is not None else (None,) * 5
 
     def lambdas_of(self, s):
         return self.lambdas[self.set_ptr[s]:self.set_ptr[s] + self.m_used[s]]
 
     def top(self, k, by="skat"):
-        """The k sets with the largest neglog10p_skat (by="burden": neglog10p_burden), falling; ties by index; sets without a value never."""
-        a = np.asarray(self.neglog10p_burden if by == "burden" else self.neglog10p_skat)
+        """The k sets with the largest neglog10p_skat (by="burden": neglog10p_burden; by="skato_o": neglog10p_skato, which needs
+        skato=True), falling; ties by index; sets without a value never."""
+        if by == "skato_o" and self.neglog10p_skato is None:
+            raise ValueError("top(by=\"skato_o\") needs a result of skato=True")
+        a = np.asarray(self.neglog10p_burden if by == "burden" else self.neglog10p_skato if by == "skato_o" else self.neglog10p_skat)
         ok = np.flatnonzero(~np.isnan(a))
         return ok[np.lexsort((ok, -a[ok]))][:int(k)]
 

@@ -1,5 +1,5 @@
 // assoc.h -- where the driver of the association scan (assoc.hip) and its passes meet (assoc_spa.hip: the selection and the
-// saddlepoint pass, assoc_firth.hip: the Firth pass, assoc_sets.hip: the set pass): the view of a handle's columns and the one
+// saddlepoint pass, assoc_firth.hip: the Firth pass, assoc_sets.hip: the set pass, assoc_skato.hip: SKAT-O on top of it): the view of a handle's columns and the one
 // dispatch on its kind, what each entry point adds to a call and what each pass hands back, and what the plain scan leaves for
 // the passes.  The device code the kernels share is assoc_slab.h.
 #pragma once
@@ -116,15 +116,23 @@ struct FirthOut {                                // all p; evals 0 where not tri
 MIH_LOCAL int assoc_firth_run(const AssocScan &sc, const AssocFlagged &fl, FirthOut &out);
 MIH_LOCAL void firth_publish(const FirthCall &call, const FirthOut &out);
 
-// mih_assoc_sets (nullptr: no set pass)
+// what mih_assoc_sets_skato adds to a set pass: the grid (rho = NULL: the default grid) and the SKAT-O outputs
+struct SkatoCall {
+    int32_t nrho; const double *rho;
+    double *neglog10p_skato, *skato_rho; uint8_t *skato_state; double *neglog10p_rho, *lambda_rho;
+};
+// mih_assoc_sets (nullptr: no set pass); skato (nullptr: no SKAT-O) is mih_assoc_sets_skato's
 struct SetsCall {
     int32_t nsets; const int64_t *set_ptr; const int32_t *set_col; const double *omega;
     int32_t *m_used; double *burden_z, *neglog10p_burden, *skat_q, *neglog10p_skat; uint8_t *skat_state; double *lambda, *cov;
+    const SkatoCall *skato;
 };
 struct SetsOut {
     std::vector<int32_t> m_used;
     std::vector<double> burden_z, nlp_burden, skat_q, nlp_skat, lambda, cov;
     std::vector<uint8_t> state;
+    std::vector<double> nlp_skato, skato_rho, nlp_rho, lambda_rho;          // SKAT-O: nsets, nsets, nsets x nrho, (nrho + 1) x entries
+    std::vector<uint8_t> skato_state;
 };
 // MIH_OK, or MIH_BAD_ARG with the error text set: a null array, nsets < 0, a malformed set_ptr, a set of more than
 // kSymEigMaxOrder entries, a column outside [0, p), columns of a set not strictly ascending, an omega negative or not finite
@@ -134,5 +142,19 @@ MIH_LOCAL int assoc_sets_check(const SetsCall &call, int64_t p);
 MIH_LOCAL double assoc_sets_bytes(const SetsCall &call, int c, double *resident);
 MIH_LOCAL int assoc_sets_run(const AssocScan &sc, const SetsCall &call, SetsOut &out);
 MIH_LOCAL void sets_publish(const SetsCall &call, const SetsOut &out);
+
+// The SKAT-O pass (assoc_skato.hip), run by assoc_sets_run on what the set pass left on the device (stream s): the lists, K,
+// T / S / Q per set (stat), the offsets of the sets' K and Jacobi slabs, and on the host m_used, stat and the SKAT results in out.
+struct SetsDevice {
+    hipStream_t s; const mih_mat *h;
+    const int64_t *set_ptr, *koff, *moff; const int32_t *m_used, *mlist; const double *omega, *Kb, *stat;
+    int64_t nslab;                               // doubles of all Jacobi slabs of one matrix per set: moff[nsets]
+    const double *stat_host;
+};
+MIH_LOCAL int assoc_skato_check(const SkatoCall &call);
+// device memory assoc_skato_run allocates: R + 1 Jacobi slabs per large set, lambda_rho, the grid and the integrands
+MIH_LOCAL double assoc_skato_bytes(const SetsCall &call, int64_t nslab);
+MIH_LOCAL int assoc_skato_run(const SetsDevice &dev, const SetsCall &call, SetsOut &out);
+MIH_LOCAL void skato_publish(const SetsCall &call, const SetsOut &out);
 
 }  // namespace mih

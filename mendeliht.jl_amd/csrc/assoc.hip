@@ -691,7 +691,18 @@ int mih_assoc_sets(const mih_mat *h, const double *A, const double *w, const dou
                    int32_t *m_used, double *burden_z, double *neglog10p_burden, double *skat_q, double *neglog10p_skat, uint8_t *skat_state,
                    double *lambda, double *cov)
 {
-    const SetsCall sets = {nsets, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambda, cov};
+    const SetsCall sets = {nsets, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambda, cov, nullptr};
+    return assoc_score_run(AssocCall{h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, nullptr, nullptr, &sets});
+}
+
+int mih_assoc_sets_skato(const mih_mat *h, const double *A, const double *w, const double *Z, int32_t c, int64_t slice_rows, int32_t nsets,
+                         const int64_t *set_ptr, const int32_t *set_col, const double *omega, int32_t nrho, const double *rho, double *z, double *beta,
+                         double *se, double *neglog10p, int32_t *m_used, double *burden_z, double *neglog10p_burden, double *skat_q,
+                         double *neglog10p_skat, uint8_t *skat_state, double *lambda, double *cov, double *neglog10p_skato, double *skato_rho,
+                         uint8_t *skato_state, double *neglog10p_rho, double *lambda_rho)
+{
+    const SkatoCall skato = {nrho, rho, neglog10p_skato, skato_rho, skato_state, neglog10p_rho, lambda_rho};
+    const SetsCall sets = {nsets, set_ptr, set_col, omega, m_used, burden_z, neglog10p_burden, skat_q, neglog10p_skat, skat_state, lambda, cov, &skato};
     return assoc_score_run(AssocCall{h, A, 1, w, Z, c, slice_rows, z, beta, se, neglog10p, nullptr, nullptr, nullptr, &sets});
 }
 

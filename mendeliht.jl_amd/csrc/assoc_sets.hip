@@ -12,9 +12,9 @@
 // and the host finishes with mixture_tail.h.  Nothing in it depends on slice_rows, on the position of a set in the list or on the
 // other sets of the call: every C_jk is ONE chain of fused multiply-adds over the rows in ascending order (no split over rows, no
 // atomics), everything after it has a fixed operation order with contraction off.
+#include "assoc_set_eig.h"
 #include "assoc_slab.h"
 #include "mixture_tail.h"
-#include "sym_eig.h"
 #include <cmath>
 #include <limits>
 
@@ -26,7 +26,6 @@ constexpr int kSetChunk = 32;                    // rows of a decode chunk: eigh
 constexpr int kSetLd = kSymEigMaxOrder + 16;     // doubles between two rows of the chunk in LDS: 288 dwords = 32 banks mod 64, so the
                                                  // four row groups of a fragment read (lane >> 4) fall on the two halves of the banks
 constexpr int kSetBlocksPerWave = 9;             // 8 x 9 / 2 = 36 lower-triangular 16 x 16 blocks over four waves
-constexpr int kSetEigLds = 64;                   // a set of up to 64 members has its M in LDS; a larger one in a global slab
 
 // ---- u ---------------------------------------------------------------------------------------------------------------------------------
 // one thread per entry e: Ub[e c + k] = sum_{l <= k} Linv[k][l] b_l of column set_col[e], l ascending (k_assoc_var's expression)
@@ -159,13 +158,6 @@ k_assoc_set_gram(ColView mt, int64_t n, const int64_t *__restrict__ set_ptr, con
 }
 
 // ---- K, T, S, Q --------------------------------------------------------------------------------------------------------------------------
-// M_jk for j >= k is (omega_j K_jk) omega_k, mirrored: one value for both triangles
-__device__ __forceinline__ double set_m_entry(const double *K, int m, const double *om, int j, int k)
-{
-#pragma clang fp contract(off)
-    return j >= k ? (om[j] * K[j * m + k]) * om[k] : (om[k] * K[k * m + j]) * om[j];
-}
-
 // One workgroup per set.  K_jk = C_jk - sum_l u_jl u_kl (l ascending from 0.0) for j > k, written to both triangles; K_jj = V_j.
 // Then rs_j = sum_k M_jk (k ascending), S = sum_j rs_j (j ascending); with a_j = omega_j U_j: T = sum_j a_j, Q = sum_j a_j a_j.
 // stat[3 s ..] = T, S, Q (zeros for a set without members).
@@ -216,29 +208,9 @@ k_assoc_set_k(const int64_t *__restrict__ set_ptr, const int32_t *__restrict__ s
 }
 
 // ---- the eigenvalues ---------------------------------------------------------------------------------------------------------------------
-// red[0] becomes the sum of the 256 values over the fixed tree; every thread gets it
-__device__ __forceinline__ double set_block_sum(double *red, double v)
-{
-#pragma clang fp contract(off)
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + k];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // One workgroup per set: the eigenvalues of M (m x m), descending, every value <= 0 set to 0, into lam[e0 ..]; NaN after m.
-// Two-sided Jacobi with the round-robin parallel ordering: the order me = m rounded up to even (a zero row and column pad an
-// odd m), me - 1 steps a sweep, step t pairing (me - 1, t) and ((t + k) mod (me - 1), (t - k) mod (me - 1)), k = 1 .. me / 2 - 1.
-// A step computes the me / 2 rotations from the matrix as it stands (sym_eig_jacobi's expressions; a pair at or below
-// u |M|_F / m is left alone), then every 2 x 2 block (pair A, pair B), B <= A, is transformed by ONE thread,
-// Z = J_A' (X J_B), and mirrored; the diagonal block becomes diag(a_pp - t a_pq, a_qq + t a_pq).  A sweep ends the iteration when
-// the off-diagonal norm has fallen to u |M|_F (sym_eig_jacobi's rule), kSymEigMaxSweeps at most; a NaN or an infinity in M gives
-// all NaN.  The order of the rotations and of every sum is fixed and contraction is off: the values are reproducible bit for bit.
-// The matrix lives in LDS up to kSetEigLds members, in the set's slab of Mb (moff[s], (ms + 1)^2 doubles) beyond.
+// The iteration is set_jacobi_eig (assoc_set_eig.h).  The matrix lives in LDS up to kSetEigLds members, in the set's slab of Mb
+// (moff[s], (ms + 1)^2 doubles) beyond.
 __global__ void __launch_bounds__(256)
 k_assoc_set_eig(const int64_t *__restrict__ set_ptr, const double *__restrict__ omega, const int64_t *__restrict__ koff, const int64_t *__restrict__ moff,
                 const int32_t *__restrict__ m_used, const int32_t *__restrict__ mlist, const double *__restrict__ Kb, double *__restrict__ Mb,
@@ -246,10 +218,7 @@ k_assoc_set_eig(const int64_t *__restrict__ set_ptr, const double *__restrict__ 
 {
 #pragma clang fp contract(off)
     __shared__ double sa[kSetEigLds * (kSetEigLds + 1)];
-    __shared__ double red[256];
-    __shared__ double om[kSymEigMaxOrder], dg[kSymEigMaxOrder];
-    __shared__ double rc[kSymEigMaxOrder / 2], rsn[kSymEigMaxOrder / 2], rd0[kSymEigMaxOrder / 2], rd1[kSymEigMaxOrder / 2];
-    __shared__ int rp[kSymEigMaxOrder / 2], rq[kSymEigMaxOrder / 2], rv[kSymEigMaxOrder / 2];
+    __shared__ double om[kSymEigMaxOrder];
     const int tid = threadIdx.x;
     const int64_t s = blockIdx.x, e0 = set_ptr[s];
     const int ms = min((int)(set_ptr[s + 1] - e0), kSymEigMaxOrder);
@@ -257,7 +226,7 @@ k_assoc_set_eig(const int64_t *__restrict__ set_ptr, const double *__restrict__ 
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (int i = tid; i < ms; i += 256) if (i >= m) lam[e0 + i] = nan;
     if (m <= 0) return;
-    const int me = (m + 1) & ~1, h = me / 2, lda = m <= kSetEigLds ? kSetEigLds + 1 : me;
+    const int me = (m + 1) & ~1, lda = m <= kSetEigLds ? kSetEigLds + 1 : me;
     double *a = m <= kSetEigLds ? sa : Mb + moff[s];
     if (tid < m) om[tid] = omega[e0 + mlist[e0 + tid]];
     __syncthreads();
@@ -269,70 +238,13 @@ k_assoc_set_eig(const int64_t *__restrict__ set_ptr, const double *__restrict__ 
         a[i * lda + j] = v;
         f2 = f2 + v * v;
     }
-    const double fro = sqrt(set_block_sum(red, f2));
-    if (!(fro <= std::numeric_limits<double>::max())) {              // a NaN or an infinity: nothing to decompose
-        if (tid < m) lam[e0 + tid] = nan;
-        return;
-    }
-    const double u = 1.1102230246251565e-16, skip = u * fro / (double)m;
-    for (int sweeps = 0;; ++sweeps) {
-        double o2 = 0.0;
-        for (int idx = tid; idx < me * me; idx += 256) {
-            const int i = idx / me, j = idx % me;
-            if (i != j) o2 = o2 + a[i * lda + j] * a[i * lda + j];
-        }
-        const double off = sqrt(set_block_sum(red, o2));
-        if (off <= u * fro || sweeps == kSymEigMaxSweeps) break;
-        for (int t = 0; t < me - 1; ++t) {
-            if (tid < h) {
-                int p = tid == 0 ? me - 1 : (t + tid) % (me - 1), q = tid == 0 ? t : (t - tid + (me - 1)) % (me - 1);
-                if (p > q) { const int x = p; p = q; q = x; }
-                const double apq = a[p * lda + q], app = a[p * lda + p], aqq = a[q * lda + q];
-                const bool on = fabs(apq) > skip;
-                double cc = 1.0, sn = 0.0, tp = 0.0;
-                if (on) {
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + hypot(theta, 1.0));
-                    cc = 1.0 / hypot(tt, 1.0); sn = tt * cc; tp = tt * apq;
-                }
-                rp[tid] = p; rq[tid] = q; rv[tid] = on ? 1 : 0; rc[tid] = cc; rsn[tid] = sn; rd0[tid] = app - tp; rd1[tid] = aqq + tp;
-            }
-            __syncthreads();
-            for (int idx = tid; idx < h * h; idx += 256) {
-                const int A = idx / h, B = idx % h;
-                if (B > A) continue;
-                const int pa = rp[A], qa = rq[A], pb = rp[B], qb = rq[B];
-                if (A == B) {
-                    if (rv[A]) { a[pa * lda + pa] = rd0[A]; a[qa * lda + qa] = rd1[A]; a[pa * lda + qa] = 0.0; a[qa * lda + pa] = 0.0; }
-                    continue;
-                }
-                if (!rv[A] && !rv[B]) continue;
-                const double ca = rc[A], sa_ = rsn[A], cb = rc[B], sb = rsn[B];
-                const double xpp = a[pa * lda + pb], xpq = a[pa * lda + qb], xqp = a[qa * lda + pb], xqq = a[qa * lda + qb];
-                const double ypp = cb * xpp - sb * xpq, ypq = sb * xpp + cb * xpq, yqp = cb * xqp - sb * xqq, yqq = sb * xqp + cb * xqq;
-                const double zpp = ca * ypp - sa_ * yqp, zqp = sa_ * ypp + ca * yqp, zpq = ca * ypq - sa_ * yqq, zqq = sa_ * ypq + ca * yqq;
-                a[pa * lda + pb] = zpp; a[pb * lda + pa] = zpp;
-                a[pa * lda + qb] = zpq; a[qb * lda + pa] = zpq;
-                a[qa * lda + pb] = zqp; a[pb * lda + qa] = zqp;
-                a[qa * lda + qb] = zqq; a[qb * lda + qa] = zqq;
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    if (tid < m) dg[tid] = a[tid * lda + tid];
-    __syncthreads();
-    if (tid < m) {                                                     // descending, equal values by index
-        const double d = dg[tid];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += (dg[j] > d || (dg[j] == d && j < tid)) ? 1 : 0;
-        lam[e0 + rank] = d > 0.0 ? d : (d == d ? 0.0 : d);
-    }
+    set_jacobi_eig(a, lda, m, f2, lam + e0);
 }
 
 // ---- the driver ------------------------------------------------------------------------------------------------------------------------
 int assoc_sets_check(const SetsCall &sc, int64_t p)
 {
+    if (sc.skato) MIH_TRY(assoc_skato_check(*sc.skato));
     if (sc.nsets < 0) { set_error("mih_assoc_sets: nsets must not be negative, got %d", (int)sc.nsets); return MIH_BAD_ARG; }
     if (!sc.set_ptr || !sc.m_used || !sc.burden_z || !sc.neglog10p_burden || !sc.skat_q || !sc.neglog10p_skat || !sc.skat_state) {
         set_error("mih_assoc_sets: null argument"); return MIH_BAD_ARG;
@@ -376,7 +288,7 @@ double assoc_sets_bytes(const SetsCall &sc, int c, double *resident)
     std::vector<int64_t> koff, moff;
     sets_offsets(sc, koff, moff);
     const double nent = (double)sc.set_ptr[sc.nsets], ns = (double)sc.nsets;
-    const double res = 8.0 * ((double)koff[(size_t)sc.nsets] + (double)moff[(size_t)sc.nsets]);
+    const double res = 8.0 * ((double)koff[(size_t)sc.nsets] + (double)moff[(size_t)sc.nsets]) + (sc.skato ? assoc_skato_bytes(sc, moff[(size_t)sc.nsets]) : 0.0);
     if (resident) *resident = res;
     return res + nent * (4.0 + 8.0 + 8.0 * c + 4.0 + 8.0)             // set_col, omega, u, the member lists, lambda
          + ns * (8.0 + 8.0 + 8.0 + 4.0 + 24.0) + 64.0;                 // set_ptr, the two offsets, m_used, T / S / Q
@@ -394,6 +306,11 @@ int assoc_sets_run(const AssocScan &scan, const SetsCall &sc, SetsOut &out)
     const double nan = std::numeric_limits<double>::quiet_NaN();
     out.burden_z.assign((size_t)ns, nan); out.nlp_burden.assign((size_t)ns, nan); out.skat_q.assign((size_t)ns, nan); out.nlp_skat.assign((size_t)ns, nan);
     out.lambda.assign((size_t)nent, nan);
+    if (sc.skato) {
+        const size_t R = (size_t)sc.skato->nrho;
+        out.nlp_skato.assign((size_t)ns, nan); out.skato_rho.assign((size_t)ns, nan); out.skato_state.assign((size_t)ns, 0);
+        out.nlp_rho.assign((size_t)ns * R, nan); out.lambda_rho.assign((size_t)nent * (R + 1), nan);
+    }
     if (ns == 0) return MIH_OK;
     std::vector<int64_t> koff, moff;
     sets_offsets(sc, koff, moff);
@@ -455,6 +372,10 @@ int assoc_sets_run(const AssocScan &scan, const SetsCall &sc, SetsOut &out)
         out.burden_z[(size_t)k] = b.z; out.nlp_burden[(size_t)k] = b.neglog10p;
         out.skat_q[(size_t)k] = stat[(size_t)k * 3 + 2]; out.nlp_skat[(size_t)k] = r.neglog10p; out.state[(size_t)k] = (uint8_t)r.state;
     }
+    if (sc.skato) {
+        const SetsDevice dev = {s, h, ptr_d.p, koff_d.p, moff_d.p, mused_d.p, mlist_d.p, om_d.p, Kb.p, stat_d.p, nm, stat.data()};
+        MIH_TRY(assoc_skato_run(dev, sc, out));
+    }
     if (sc.cov) {                              // K over the entries of every set, NaN in the rows and columns of non-members
         out.cov.assign((size_t)nk, nan);
         for (int64_t k = 0; k < ns; ++k) {
@@ -481,6 +402,7 @@ void sets_publish(const SetsCall &call, const SetsOut &out)
     memcpy(call.skat_state, out.state.data(), ns);
     if (call.lambda && !out.lambda.empty()) memcpy(call.lambda, out.lambda.data(), sizeof(double) * out.lambda.size());
     if (call.cov && !out.cov.empty()) memcpy(call.cov, out.cov.data(), sizeof(double) * out.cov.size());
+    if (call.skato) skato_publish(call, out);
 }
 
 }  // namespace mih

@@ -47,7 +47,7 @@ constexpr double kMixNearMean = 9.094947017729282e-13;   // 2^-40: w^2 below thi
 constexpr int kMixMaxEvals = 128;
 
 // log Phi(-r) for any r, by the arithmetic of neglog10p_of_z
-inline double mix_log_phi_neg(double r)
+MIH_TAIL_FN double mix_log_phi_neg(double r)
 {
     const double x = std::fabs(r) * 0.7071067811865476 /* 1 / sqrt 2 */, ln2 = 0.6931471805599453;
     if (std::isnan(x)) return x;
@@ -60,7 +60,7 @@ inline double mix_log_phi_neg(double r)
 
 struct MixIter { double s, lo, hi, shat; int evals, status; };      // status: 0 running, 1 converged, 2 gave up
 
-inline void mix_eval(int m, const double *lambda, double s, double *g, double *g2)
+MIH_TAIL_FN void mix_eval(int m, const double *lambda, double s, double *g, double *g2)
 {
     const double l1 = lambda[0];
     double a = 0.0, b = 0.0;
@@ -73,7 +73,7 @@ inline void mix_eval(int m, const double *lambda, double s, double *g, double *g
 }
 
 // the root iteration of the header comment; lambda[0] > 0 and finite, q > 0
-inline void mix_root(int m, const double *lambda, double q, MixIter &it)
+MIH_TAIL_FN void mix_root(int m, const double *lambda, double q, MixIter &it)
 {
     it.s = 0.0; it.lo = -HUGE_VAL; it.hi = 1.0; it.shat = std::nan(""); it.evals = 0; it.status = 0;
     const double tol = kMixTolF * q;
@@ -97,7 +97,7 @@ inline void mix_root(int m, const double *lambda, double q, MixIter &it)
 struct MixResult { double neglog10p, t_hat; int state, evals; };
 
 // the SKAT tail of one set: lambda (m, descending, >= 0 or NaN), Q
-inline MixResult mixture_tail(int m, const double *lambda, double Q)
+MIH_TAIL_FN MixResult mixture_tail(int m, const double *lambda, double Q)
 {
     const double nan = std::nan(""), inv_ln10 = 0.4342944819032518;
     MixResult r = {nan, nan, 0, 0};
@@ -140,7 +140,7 @@ inline MixResult mixture_tail(int m, const double *lambda, double Q)
 struct BurdenResult { double z, neglog10p; };
 
 // burden_z = T / sqrt S, NaN where S <= 0 (or is NaN); the two-sided normal tail
-inline BurdenResult burden_tail(double T, double S)
+MIH_TAIL_FN BurdenResult burden_tail(double T, double S)
 {
     BurdenResult b;
     b.z = S > 0.0 ? T / std::sqrt(S) : std::nan("");

@@ -3,6 +3,13 @@
 #pragma once
 #include <cmath>
 
+// the tails are host code; the integrand of SKAT-O (assoc_skato.hip) evaluates them on the device as well
+#ifdef __HIPCC__
+#define MIH_TAIL_FN __host__ __device__ inline
+#else
+#define MIH_TAIL_FN inline
+#endif
+
 namespace mih {
 
 // x >= kTailSwitch: log erfc(x) from Laplace's continued fraction
@@ -13,7 +20,7 @@ namespace mih {
 constexpr double kTailSwitch = 25.0;
 constexpr int kTailTerms = 24;
 
-inline double log_erfc_tail(double x)
+MIH_TAIL_FN double log_erfc_tail(double x)
 {
     double f = x;
     for (int k = kTailTerms; k >= 1; --k) f = x + (0.5 * k) / f;
@@ -22,7 +29,7 @@ inline double log_erfc_tail(double x)
 
 // -log10 of p = erfc(|z| / sqrt 2), the two-sided p-value of a standard normal z.  NaN for a NaN, +inf for an infinite z.
 // Small |z|: p = 1 - erf(x) is formed through log1p so that the result keeps its relative accuracy down to z = 0 (which gives 0).
-inline double neglog10p_of_z(double z)
+MIH_TAIL_FN double neglog10p_of_z(double z)
 {
     if (std::isnan(z)) return z;
     const double x = std::fabs(z) * 0.7071067811865476 /* 1 / sqrt 2 */;

@@ -7,7 +7,9 @@ matrix-core rate it reaches over the padded blocks.
     python tools/bench_assoc_sets.py               # 500 000 x 1 000 000, 20 000 sets of 50
     python tools/bench_assoc_sets.py --small       # 100 000 x 20 000, 400 sets of 50
     python tools/bench_assoc_sets.py --floor       # 20 000 x 200, 4 sets of 50: the device call against export_bed() -> the numpy
-                                                   # statement (tests/sets_spec.py)"""
+                                                   # statement (tests/sets_spec.py)
+    python tools/bench_assoc_sets.py --skato       # any of the shapes: beside the plain set call, the call with SKAT-O on the
+                                                   # default grid (csrc/assoc_skato.hip), its two kernels and the ratio of the calls"""
 import argparse
 import json
 import os
@@ -23,13 +25,14 @@ import mendeliht_amd as m  # noqa: E402
 from tools.bench_assoc_spa import inputs  # noqa: E402
 
 
-def timed(x, null, Z, sets):
+def timed(x, null, Z, sets, skato=False):
     m.profile_passes(x)
     t0 = time.perf_counter()
-    res = x.set_test(null.A, null.w, Z, sets)
+    res = x.set_test(null.A, null.w, Z, sets, skato=skato)
     t = time.perf_counter() - t0
     recs = m.profile_passes(x)
-    return t, sum(r["ms"] for r in recs if r["kernel"] == "k_assoc_set_gram"), sum(r["ms"] for r in recs if r["kernel"] == "k_assoc_set_eig"), res
+    ms = lambda name: sum(r["ms"] for r in recs if r["kernel"] == name)
+    return t, ms("k_assoc_set_gram"), ms("k_assoc_set_eig"), res, ms("k_assoc_set_rho"), ms("k_assoc_set_skato")
 
 
 def host_route(x, null, Z, sets):
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("--cases", type=float, default=0.01)
     ap.add_argument("--small", action="store_true", help="100 000 x 20 000, 400 sets")
     ap.add_argument("--floor", action="store_true", help="20 000 x 200, 4 sets, timed against the host route")
+    ap.add_argument("--skato", action="store_true", help="time the call with SKAT-O on the default grid as well")
     ap.add_argument("--seed", type=int, default=5)
     a = ap.parse_args()
     n, p, ns = (20_000, 200, 4) if a.floor else (100_000, 20_000, 400) if a.small else (a.n, a.p, a.sets)
@@ -74,6 +78,7 @@ def main():
         plain.append(time.perf_counter() - t0)
     m.profile_enable(x, True)
     runs = [timed(x, null, Z, sets) for _ in range(3)]
+    oruns = [timed(x, null, Z, sets, skato=True) for _ in range(4)][1:] if a.skato else []      # (the first call loads the code objects)
     m.profile_enable(x, False)
     s, gms, ems = (statistics.median(r[k] for r in runs) for k in range(3))
     last = runs[-1][3]
@@ -84,6 +89,13 @@ def main():
                members=int(mem), states=[int(v) for v in np.bincount(last.skat_state, minlength=6)],
                decoded_per_s=round(n * pad / max(gms, 1e-9) * 1e3, 0),
                gram_f64_flops_per_s=round(2.0 * 256.0 * blocks * (-(-n // 32) * 32) / max(gms, 1e-9) * 1e3, 0))
+    if a.skato:
+        so, rms, ims = (statistics.median(r[k] for r in oruns) for k in (0, 4, 5))
+        o = oruns[-1][3]
+        assert np.array_equal(o.neglog10p_skat, last.neglog10p_skat, equal_nan=True) and np.array_equal(o.lambdas, last.lambdas, equal_nan=True)
+        res.update(skato_call_s=round(so, 4), rho_kernel_ms=round(rms, 3), skato_kernel_ms=round(ims, 3), skato_over_sets=round(so / s, 3),
+                   skato_states=[int(v) for v in np.bincount(o.skato_state, minlength=5)],
+                   skato_rho_counts=[int((o.skato_rho == r).sum()) for r in (0.0, 0.01, 0.04, 0.09, 0.16, 0.25, 0.5, 1.0)])
     if a.floor:
         ref, th = host_route(x, null, Z, sets)
         same = np.array_equal(ref["skat_state"], last.skat_state) and np.array_equal(ref["m_used"], last.m_used)
