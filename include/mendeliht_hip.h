@@ -209,6 +209,22 @@ int mih_snp_counts(const mih_mat *h, const uint8_t *row_keep, const uint8_t *col
  * that is not 2-bit, an empty selection, an index out of range, indices that are not strictly increasing. */
 int mih_snp_subset(const mih_mat *h, const int64_t *rows, int64_t nrows, const int64_t *cols, int64_t ncols,
                    int center, int scale, int impute, int dtype, mih_mat **out);
+/* mih_snp_transpose: the 2-bit matrix of the TRANSPOSED genotypes -- SNPs as rows, samples as columns, n_out = p, p_out = n -- as a
+ * new, ordinary, immutable handle on the same device, made there (no genotype crosses the host link).  It is bit for bit the handle
+ * mih_snp_create builds from the .bed encoding of the transposed code matrix: the tiles with their zero pad rows and columns, mu
+ * and 1/sigma (now per SAMPLE, over its observed SNPs), the ascending missing lists and their total.  Everything that takes a 2-bit
+ * handle takes it: mih_snp_export_bed, mih_snp_counts, mih_xtv*, a fit.  Its X'r pass is the dense forward product of the source
+ * (mih_xb_dense).  The stored tile is a matrix-core operand with the row axis as K, so no image can be contracted over its columns:
+ * this second image is the way to X B.
+ * center, scale, impute, dtype: as mih_snp_create (they describe what the new handle presents).  reserve_bytes: the reserve of
+ * device memory for fits on the new handle -- 0: mih_snp_create's rule, > 0: that many bytes, < 0: none (a row image of 125 GB that
+ * only serves mih_xb_dense must not set aside 15.7 GB).
+ * Memory: one more image of ceil(n / 32) ceil(p / 128) KB (about n p / 4 bytes), 24 bytes per sample and 4 per missing genotype for
+ * the statistics and lists, and during the call 12 bytes per sample plus, with missing genotypes, 16 per SNP; the sum is compared
+ * with the free memory before anything is allocated, and MIH_OOM names both byte counts.  The source is only read.  Only integer
+ * atomics are used (counts, and an or of a constant per missing genotype): the result does not depend on the launch order.
+ * Refusals: a handle that is not 2-bit, a dtype other than 64 / 32 (MIH_BAD_ARG); p >= 2^31 (MIH_BAD_DIM). */
+int mih_snp_transpose(const mih_mat *src, int center, int scale, int impute, int dtype, int64_t reserve_bytes, mih_mat **out);
 /* The genetic relationship (kinship) matrix of the samples of a 2-bit or a 16-bit dosage handle (a dense handle: MIH_BAD_ARG),
  * made entirely on the device -- SnpArrays.grm(x; method, minmaf) and the screen for pairs with Phi > 0.125 that
  * manuscript/UKBB_metabolomic/data_process.jl:80-103 runs between SnpArrays.filter and the principal components
@@ -634,6 +650,28 @@ int mih_xtv_batched_fmt(const mih_mat *h, const double *R, int m, int digits, do
 /* out = sum_t x[:, idx[t]] * val[t]  -- the column loops of update_xb!
  * (src/utilities.jl:98-106) and iht_stepsize! (:731-739); idx 0-based. */
 int mih_xv_sparse(const mih_mat *h, const int64_t *idx, const double *val, int64_t nnz, double *out);
+/* mul!(out, x, B) for a dense B: OUT (n x t, column-major) = X * B (p x t, column-major), X as the SnpLinAlg of `h` presents it, or
+ * with the flags overridden (center / scale / impute: 0, 1, or -1 = the handle's).  rows: the handle mih_snp_transpose made from h
+ * (any flags; its tiles and lists are what is read).  digits: as mih_xtv_batched_fmt.
+ * X B = (X')' B: the X'r pass runs over the row image with the columns of a = sinv o B (B itself without scale) as its residuals --
+ * the same exact fixed point, the same 19 fused operands (any t >= 1: the pass planner cuts it into passes), the same row slices
+ * and outlier side channel -- on raw codes with missing = 0; then one thread per sample adds
+ *     + sum_{j in miss(i)} mu_j a_jt   (impute: the sample's list of the row image, ascending j, one f64 chain)
+ *     - sum_j mu_j a_jt                (center: c_t, a fixed tree over the SNPs, the same bits on every call)
+ * in this order, every operation one f64 rounding (no contraction).
+ * OUT[:, t] depends only on B[:, t], the two matrices and digits: not on which other columns share the call, not on the row slices or
+ * any other internal of the pass, not on the number of calls.  Accuracy: the pass's own (above mih_xtv_batched_fmt) -- the main term
+ * is within 2^-53 max_j |a_jt| sum_j code_ij + 64 ulp of the exact value -- plus the roundings of a, of mu a, of the chain (one per
+ * missing SNP of the sample), of the tree (at most 19 + ceil(p / 262144) per term) and of the two final additions; tests/xb_spec.py
+ * derives the elementwise bound.  A NaN or +-Inf anywhere in a column of B (or in its a), or a column whose sum overflows, gives NaN
+ * in that whole column of OUT and leaves the other columns untouched: the pass's own rule.  A SNP without an observed genotype has
+ * mu = NaN: with center or impute every entry of OUT is NaN, as every entry of that column of X is.
+ * Memory: beside the row image (mih_snp_transpose), 8 t (3 p + n) bytes and the pass's workspace, released before the call returns.
+ * Refusals (MIH_BAD_ARG, nothing written): a null pointer; h or rows not 2-bit (the products of dense and dosage handles are not
+ * offered); rows that is not the image of h -- rows->n != h->p, rows->p != h->n, another device, another number of missing
+ * genotypes: the message holds both shapes; t < 1; a flag outside -1, 0, 1; an unknown format. */
+int mih_xb_dense(const mih_mat *h, const mih_mat *rows, const double *B, int32_t t, int center, int scale, int impute,
+                 int digits, double *OUT);
 
 /* ---- projections ----------------------------------------------------------- */
 /* project_k!(x, k) src/utilities.jl:553-559: zero every |x_i| < |k-th largest|;

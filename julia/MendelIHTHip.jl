@@ -47,7 +47,9 @@ mutable struct HipSnpLinAlg{T} <: AbstractMatrix{T}
     center::Bool
     scale::Bool
     impute::Bool
+    rows::Any          # the row image mul!(out, x, B) reads (transpose_image), built on first use and kept on the object; or nothing
 end
+HipSnpLinAlg{T}(handle::Ptr{Cvoid}, n, p, center, scale, impute) where {T} = HipSnpLinAlg{T}(handle, n, p, center, scale, impute, nothing)
 
 # T = Float64 or Float32 (src/MendelIHT.jl:39).  The device matrix has no element type: T only decides what the fits hand back
 function HipSnpLinAlg{T}(s::SnpArray; center::Bool=false, scale::Bool=false,
@@ -84,6 +86,32 @@ function LinearAlgebra.mul!(out::Matrix{Float64}, xt::Transpose{Float64, HipSnpL
                 xt.parent.handle, RR, size(RR, 2), out))
     return out
 end
+
+# The 2-bit matrix of the transposed genotypes (p x n: SNPs as rows), made on the device (mih_snp_transpose); reserve < 0: no
+# reserve of device memory for fits on it.
+function transpose_image(x::HipSnpLinAlg{T}; center::Bool=x.center, scale::Bool=x.scale, impute::Bool=x.impute,
+                         reserve::Integer=0) where {T}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mih_snp_transpose, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Int64, Ref{Ptr{Cvoid}}),
+        x.handle, center, scale, impute, 8 * sizeof(T), reserve, h))
+    xt = HipSnpLinAlg{T}(h[], x.p, x.n, center, scale, impute)
+    finalizer(v -> ccall((:mih_mat_destroy, LIB), Cint, (Ptr{Cvoid},), v.handle), xt)
+    return xt
+end
+# mul!(out, x, B) for a dense B (p, or p x t): the X'r pass over the row image of x (mih_xb_dense), exact fixed point.  The image is
+# built on the first product and kept on x (x.rows = nothing drops it).
+function xb_dense!(out::VecOrMat{Float64}, x::HipSnpLinAlg{Float64}, B::AbstractVecOrMat{Float64}; xtv_digits::Int=0)
+    BB = Matrix{Float64}(reshape(B, size(B, 1), :))
+    size(BB, 1) == x.p && size(out, 1) == x.n && size(out, 2) == size(BB, 2) || throw(DimensionMismatch("mul!: sizes do not match"))
+    x.rows === nothing && (x.rows = transpose_image(x; center=false, scale=false, impute=false, reserve=-1))
+    rows = x.rows::HipSnpLinAlg{Float64}
+    GC.@preserve x rows check(ccall((:mih_xb_dense, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int32, Cint, Cint, Cint, Cint, Ptr{Float64}),
+        x.handle, rows.handle, BB, size(BB, 2), -1, -1, -1, xtv_digits, out))
+    return out
+end
+LinearAlgebra.mul!(out::Vector{Float64}, x::HipSnpLinAlg{Float64}, b::AbstractVector{Float64}) = xb_dense!(out, x, b)
+LinearAlgebra.mul!(out::Matrix{Float64}, x::HipSnpLinAlg{Float64}, B::AbstractMatrix{Float64}) = xb_dense!(out, x, B)
 
 # maf_weights(x; max_weight) (utilities.jl:682-697) from the allele means the device computed at upload (mu = 2 maf')
 function maf_weights(x::HipSnpLinAlg{Float64}; max_weight::Float64=Inf)

@@ -166,6 +166,7 @@ _SIGNATURES = {
     "mih_snp_export_bed": [_vp, _vp],
     "mih_snp_counts": [_vp, _vp, _vp, _vp, _vp],
     "mih_snp_subset": [_vp, _vp, _i64, _vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)],
+    "mih_snp_transpose": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i64, C.POINTER(_vp)],
     "mih_grm": [_vp, _vp, C.c_int, _i64, _vp],
     "mih_grm_pairs": [_vp, _vp, C.c_int, _i64, _dbl, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp],
     "mih_grm_eig": [_vp, _vp, C.c_int, _i64, _i32, _i32, _dbl, _i32, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)],
@@ -183,6 +184,7 @@ _SIGNATURES = {
     "mih_xtv_batched": [_vp, _vp, C.c_int, _vp],
     "mih_xtv_batched_fmt": [_vp, _vp, C.c_int, C.c_int, _vp],
     "mih_xv_sparse": [_vp, _vp, _vp, _i64, _vp],
+    "mih_xb_dense": [_vp, _vp, _vp, _i32, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "mih_project_topk": [_vp, _i64, _i64, C.POINTER(_i64)],
     "mih_project_group_sparse": [_vp, _vp, _i64, _i64, _vp, C.c_int],
     "mih_fit_iht": [_vp, C.POINTER(_FitParams), _vp, _vp, _i64, _vp, C.POINTER(_FitResult)],
@@ -698,6 +700,13 @@ class _Mat:
         res.assoc.null = null
         return res
 
+    # mul!(out, x, B) for a dense B: offered by the 2-bit matrix (SnpLinAlg.xb); the other kinds say so
+    def xb(self, B, xtv_digits=None, center=None, scale=None, impute=None):
+        raise ArgumentError(f"xb (the dense product X B) is offered for the 2-bit matrix (SnpLinAlg) only, not for {type(self).__name__}")
+
+    def score(self, weights, cols=None, average=False):
+        raise ArgumentError(f"score is offered for the 2-bit matrix (SnpLinAlg) only, not for {type(self).__name__}")
+
     def xv_sparse(self, idx, val):
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         val = np.ascontiguousarray(val, dtype=np.float64)
@@ -1014,6 +1023,86 @@ class SnpLinAlg(_Mat, _Kinship):
         x._reserve(reserve)
         return x
 
+    # ---- the transposed image and the dense forward product (csrc/transpose.hip, csrc/xb.hip) ----
+    def transpose(self, center=None, scale=None, impute=None, dtype=None, reserve=None):
+        """The 2-bit matrix of the transposed genotypes (SNPs as rows, samples as columns) as a new SnpLinAlg of shape (p, n), made
+        on the device (mih_snp_transpose): bit for bit the SnpLinAlg of the .bed encoding of the transposed code matrix, with mu
+        and 1/sigma per sample.  The flags default to this matrix's, like subset; reserve as in the constructor, and -1: no reserve
+        of device memory for fits whatever the size.  This matrix is unchanged."""
+        center = self.center if center is None else bool(center)
+        scale = self.scale if scale is None else bool(scale)
+        impute = self.impute if impute is None else bool(impute)
+        dtype = self.dtype if dtype is None else _snp_dtype(dtype)
+        none = reserve is not None and reserve is not True and reserve is not False and int(reserve) < 0
+        h = C.c_void_p(None)
+        _check(lib().mih_snp_transpose(self._h, int(center), int(scale), int(impute), 32 if dtype is np.float32 else 64,
+                                       -1 if none else 0, C.byref(h)))
+        x = SnpLinAlg(None, center=center, scale=scale, impute=impute, device=self.device, _handle=h, dtype=dtype)
+        if not none:
+            x._reserve(reserve)
+        return x
+
+    def row_image(self, build=True):
+        """The row image xb() reads: the transposed matrix, kept on this object as self._rows (the library has no hidden cache
+        and no process-wide state).  build=True makes it if it is not there (reserve=-1: it only serves products), build=False
+        drops it.  Returns the bytes of device memory its tiles take afterwards (0: none)."""
+        if not build:
+            self._rows = None
+            return 0
+        if getattr(self, "_rows", None) is None:
+            self._rows = self.transpose(center=False, scale=False, impute=False, reserve=-1)
+        r = self._rows
+        return ((r.p + 31) // 32) * ((r.n + 127) // 128) * 1024
+
+    def xb(self, B, xtv_digits=None, center=None, scale=None, impute=None, rows=None):
+        """mul!(out, x, B) for a dense B of length p (-> n) or shape p x t (-> n x t): X B with X as this SnpLinAlg presents it,
+        or with the flags overridden (mih_xb_dense).  The product is the X'r pass over the row image -- exact fixed point, any t,
+        19 columns a pass; a column of the result depends on its column of B alone, bit for bit.  The row image is built on the
+        first call (row_image()) and kept; rows: another SnpLinAlg made by x.transpose() to read instead.  A NaN or Inf in a
+        column of B makes that column of the result NaN."""
+        B = np.asarray(B, dtype=np.float64)
+        if B.ndim not in (1, 2) or B.shape[0] != self.p:
+            raise DimensionMismatch(f"B has shape {B.shape}, expected ({self.p},) or ({self.p}, t)")
+        if B.ndim == 2 and B.shape[1] == 0:
+            raise DimensionMismatch(f"B has shape {B.shape}: no column")
+        if rows is None:
+            self.row_image(True)
+            rows = self._rows
+        t = 1 if B.ndim == 1 else B.shape[1]
+        Bf = np.asfortranarray(B.reshape(self.p, t))
+        out = np.empty((self.n, t), order="F")
+        flag = lambda f: -1 if f is None else int(bool(f))      # noqa: E731
+        _check(lib().mih_xb_dense(self._h, rows._h, _p(Bf), t, flag(center), flag(scale), flag(impute), _digits(xtv_digits), _p(out)))
+        return out[:, 0].copy() if B.ndim == 1 else out
+
+    def score(self, weights, cols=None, average=False):
+        """`plink --score`: the polygenic score sum_j w_j g_ij of every sample, whatever this handle's flags: raw allele counts
+        (the counted allele is the one the dosages count), a missing genotype imputed by the SNP's mean dosage mu_j -- xb with
+        center 0, scale 0, impute 1.  weights: one per SNP, or one per entry of cols, an index array or boolean mask of the SNPs
+        they belong to (the others get weight 0).  average=False is the SCORESUM column of `plink --score ... sum` (SCORE1_SUM
+        of plink2); average=True divides by 2 x the number of scored SNPs: the SCORE column of PLINK 1.9's default .profile
+        (SCORE1_AVG of plink2), whose denominator under its default mean imputation is the allele count of all scored variants.
+        PLINK imputes a missing genotype by the allele frequency of the scored file, which is mu_j / 2 of this matrix: the same
+        thing when the matrix is the scored file (and not when frequencies come from elsewhere, --read-freq); its
+        `no-mean-imputation` (missing genotypes dropped from sum and denominator) is not offered."""
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim != 1:
+            raise DimensionMismatch(f"weights has shape {w.shape}, expected one dimension")
+        if cols is None:
+            if w.size != self.p:
+                raise DimensionMismatch(f"weights has length {w.size}, expected {self.p}")
+            full, scored = w, self.p
+        else:
+            idx = self._sel_indices(cols, self.p, "column")
+            if idx.size != w.size:
+                raise DimensionMismatch(f"weights has length {w.size}, cols selects {idx.size} SNPs")
+            if idx.size and (idx.min() < 0 or idx.max() >= self.p):
+                raise ArgumentError(f"a column index is outside 0 .. {self.p - 1}")
+            full, scored = np.zeros(self.p), idx.size
+            full[idx] = w
+        s = self.xb(full, center=False, scale=False, impute=True)
+        return s / (2.0 * scored) if average else s
+
     def filter(self, min_success_rate_per_row=0.98, min_success_rate_per_col=0.98, min_maf=0.01, maxiters=5):
         """SnpArrays.filter (without the Hardy-Weinberg test): boolean masks (rmask, cmask) of the rows and columns that are left
         when rows and columns below the success rates, and columns below min_maf, are dropped in turn until nothing changes or
@@ -1296,6 +1385,12 @@ class IHTResult:
         self.choose_fired = choose_fired
         self.mu = mu
 
+    def predict_eta(self, x, z=None):
+        """The linear predictor of this model on a cohort: x.xb(beta) + z @ c (z None: the intercept column of a fit without
+        covariates).  x: a SnpLinAlg with the flags of the fitted one.  The mean is the link's inverse of it."""
+        z = np.ones((x.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(x.n, -1)
+        return x.xb(np.asarray(self.beta, dtype=np.float64)) + z @ np.asarray(self.c, dtype=np.float64)
+
     def __repr__(self):
         nz = np.flatnonzero(self.beta)
         cz = np.flatnonzero(self.c)
@@ -1318,6 +1413,12 @@ class mIHTResult:
         self.Sigma, self.sigma_g = Sigma, sigma_g
         self.trace = trace or {}
         self.choose_fired = choose_fired
+
+    def predict_eta(self, x, z=None):
+        """The r x n linear predictors of this model on a cohort: (x.xb(beta')) ' + c z, beta r x p, c r x q, z q x n (None: the
+        row of ones of a fit without covariates)."""
+        z = np.ones((1, x.n)) if z is None else np.asarray(z, dtype=np.float64).reshape(-1, x.n)
+        return x.xb(np.asarray(self.beta, dtype=np.float64).T).T + np.asarray(self.c, dtype=np.float64) @ z
 
 
 class IHTSession:

@@ -397,6 +397,10 @@ int alloc_snp(mih_mat *h);
 int finish_counts(mih_mat *h, const int32_t *cnt_dev);
 int finish_tiles(mih_mat *h, const int32_t *cnt_dev);
 void reserve_fit_memory(mih_mat *h, bool asked = false, size_t asked_bytes = 0);
+// qc.hip: k_missing_counts over the whole matrix, queued on s -- cnt4[4 j + 3] the missing entries of every kept column (room for
+// 4 p counters, zeroed by the caller) and row_missing[i] those of every kept row (may be nullptr); the masks are device pointers
+MIH_LOCAL void launch_missing_counts(const mih_mat *h, const uint8_t *row_keep_dev, const uint8_t *col_keep_dev, int32_t *cnt4,
+                                     int32_t *row_missing, hipStream_t s);
 constexpr int kWorkerStreamsPerLane = 4;       // the runtime maps streams onto a handful of hardware queues anyway
 // stream i of the matrix's worker set (i < 2 * kWorkerStreamsPerLane); nullptr if it cannot be created
 hipStream_t worker_stream(const mih_mat *h, int i);
@@ -498,6 +502,8 @@ struct XtvWork {            // scratch for one in-flight X'r
     DigitMode dm_alt = {49, 8, 4, 8, 42, 18}; bool has_alt = false, use_alt = false;
     XtvSupportHook hook;       // ... and whose finalize kernel also serves the support of the iterate
     XtvStatsHook shook;        // ... and whose digit kernel finishes those statistics
+    bool raw = false;          // the finalize kernel leaves the dots of the stored codes (missing = 0): no centring, scaling or imputation,
+                               // whatever the handle's flags (xb.hip: the pass over a row image, whose corrections live on the other axis)
     // the matrix's score image, pinned for the life of the workspace (single-residual 428 workspaces only), and its scratch
     std::shared_ptr<const ScoreImage> img;
     DevBuf<unsigned long long> hom_u;   // n_pad : U of every row (k_digits)

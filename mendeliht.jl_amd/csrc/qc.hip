@@ -211,6 +211,19 @@ k_kept_missing(const int64_t *__restrict__ s_ptr, const int32_t *__restrict__ s_
     if (!out && lane == 0) cnt[3 * j + 2] = c;
 }
 
+void launch_missing_counts(const mih_mat *h, const uint8_t *row_keep_dev, const uint8_t *col_keep_dev, int32_t *cnt4,
+                           int32_t *row_missing, hipStream_t s)
+{
+    const int64_t n = h->n, p = h->p;
+    const int64_t slab = 65535ll * kQcListCols;                  // (grid.y stays below 65536)
+    for (int64_t c0 = 0; c0 < p; c0 += slab) {
+        const int64_t nc = std::min(slab, p - c0);
+        dim3 grid((unsigned)((n + kQcListRows - 1) / kQcListRows), (unsigned)((nc + kQcListCols - 1) / kQcListCols));
+        hipLaunchKernelGGL(k_missing_counts, grid, dim3(512), 0, s, h->miss_ptr + c0, h->miss_row, n, nc, row_keep_dev,
+                           col_keep_dev ? col_keep_dev + c0 : nullptr, cnt4 + 4 * c0, row_missing);
+    }
+}
+
 // a selection (strictly increasing 0-based indices below `len`, or nullptr for everything): how many, or -1 with the error set
 static int64_t check_selection(const char *what, const int64_t *idx, int64_t count, int64_t len)
 {
@@ -270,15 +283,7 @@ int mih_snp_counts(const mih_mat *h, const uint8_t *row_keep, const uint8_t *col
         hipLaunchKernelGGL(k_masked_counts, dim3((unsigned)(h->ncg * nchunk)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(h->X), h->nbp, p,
                            nchunk, reinterpret_cast<const uint4 *>(mask.p), ck.p, cnt.p);
     }
-    if (h->total_missing > 0) {
-        const int64_t slab = 65535ll * kQcListCols;              // (grid.y stays below 65536)
-        for (int64_t c0 = 0; c0 < p; c0 += slab) {
-            const int64_t nc = std::min(slab, p - c0);
-            dim3 grid((unsigned)((n + kQcListRows - 1) / kQcListRows), (unsigned)((nc + kQcListCols - 1) / kQcListCols));
-            hipLaunchKernelGGL(k_missing_counts, grid, dim3(512), 0, s, h->miss_ptr + c0, h->miss_row, n, nc, rk.p, ck.p ? ck.p + c0 : nullptr,
-                               cnt.p + 4 * c0, rm.p);
-        }
-    }
+    if (h->total_missing > 0) launch_missing_counts(h, rk.p, ck.p, cnt.p, rm.p, s);
     if (col_counts) MIH_HIP(hipMemcpyAsync(col_counts, cnt.p, sizeof(int32_t) * 4 * (size_t)p, hipMemcpyDeviceToHost, s));
     if (row_missing) MIH_HIP(hipMemcpyAsync(row_missing, rm.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     MIH_HIP(hipStreamSynchronize(s));

@@ -402,7 +402,7 @@ int xtv_device(const mih_mat *h, XtvWork &w, const double *r_dev, int m, double 
         if (rc) return rc;
         hipLaunchKernelGGL(k_xtv_finalize, dim3((unsigned)((h->p + 255) / 256 + (hooked ? w.hook.blocks : 0))), dim3(256), 0, s,
                            partial, splits, pstride, h->p, ps.u1 - ps.u0, w.scal.p + 4 * ps.u0, r_dev + (int64_t)ps.u0 * h->n, h->n, h->mu, h->sinv,
-                           h->miss_ptr, h->miss_row, h->center, h->scale, h->impute && h->total_missing > 0, out_dev + (int64_t)ps.u0 * h->p,
+                           h->miss_ptr, h->miss_row, w.raw ? 0 : h->center, w.raw ? 0 : h->scale, !w.raw && h->impute && h->total_missing > 0, out_dev + (int64_t)ps.u0 * h->p,
                            w.gate, w.gate_val, hooked ? w.hook : XtvSupportHook(), w.peel.p + (int64_t)ps.u0 * kPeelStride, h->X, h->nbp);
     }
     MIH_HIP(hipGetLastError());
