@@ -273,6 +273,57 @@ int mih_grm_pairs(const mih_mat *h, const uint8_t *col_keep, int method, int64_t
 int mih_grm_eig(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, int32_t k, int32_t block, double tol,
                 int32_t max_iter, uint64_t seed, double *values /* k */, double *vectors /* n x k, column-major */,
                 double *residuals /* k */, int32_t *iters, int32_t *converged);
+/* Linear solves with the variance matrix of a mixed model on that Phi, V = tau_e I + tau_g Phi (tau_e > 0, tau_g >= 0): the
+ * building block of the variance-component null model that SAIGE, fastGWA and GMMAT fit on related samples -- without Phi
+ * leaving the device and without an n x n factorisation.  h, col_keep, method and panel_cols are mih_grm's.  B (n x m,
+ * column-major, host, 1 <= m <= 128): the right-hand sides; X (n x m, column-major): X ~ V^-1 B.  Per column c: iters[c] the
+ * iterations taken, converged[c] whether the recurrence residual reached |r|_2 <= tol |b|_2, residuals[c] the true residual
+ * |b - V x|_2, formed explicitly with one more product.  Reaching max_iter is no error: the last iterate comes back with
+ * converged[c] = 0 and its residual.  A zero column b gives x = 0, 0 iterations, converged.
+ * The method (tests/lmm_spec.py states it in numpy): Phi, mirrored to the full symmetric n_pad x n_pad matrix, stays in device
+ * memory; a conjugate gradient with the Jacobi preconditioner diag V = tau_e + tau_g Phi_ii from x = 0, every column with its
+ * own scalars, V p once per iteration on the f64 matrix pipe; a column that has converged is frozen and the call ends when
+ * all are, or at max_iter.  The scalars and the flags stay in device memory; every sum runs in an order that n_pad alone
+ * fixes, without atomics: a column of X is bit for bit the same whatever the other columns of B, whatever m and panel_cols,
+ * and on repeated calls.
+ * Device memory: mih_grm's plus 8 (6 n_pad bp + n_pad + bp (n_pad / 16 + n_pad / 64 + 5)) + 4 (3 bp + 1) bytes, bp = m rounded
+ * up to 16, checked in the same way before anything is allocated (MIH_OOM names both byte counts).
+ * Refusals, MIH_BAD_ARG with nothing allocated and nothing written: everything mih_grm refuses; m < 1 or m > 128; tau_e not
+ * finite or not positive; tau_g not finite or negative; tol not finite or negative; max_iter < 1; a null pointer. */
+int mih_grm_solve(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, double tau_e, double tau_g,
+                  const double *B /* n x m, column-major */, int32_t m, double tol, int32_t max_iter,
+                  double *X /* n x m, column-major */, int32_t *iters /* m */, int32_t *converged /* m */, double *residuals /* m */);
+/* The variance-component null model of a mixed-model association scan for one Normal trait on that Phi, built once per call:
+ * y = Z alpha + g + e, g ~ N(0, tau_g Phi), e ~ N(0, tau_e I), fitted by average-information REML as GMMAT and SAIGE do
+ * (tests/lmm_spec.py states every step in numpy).  y (n), Z (n x c, column-major, full column rank, give the intercept), probes
+ * Rademacher vectors for Hutchinson's trace estimates, 1 <= probes <= 64 and 1 + c + probes <= 128, hashed on the device from
+ * (seed, row, probe).  Start: e0 the OLS residual, s2 = e0'e0 / (n - c), dbar = mean Phi_ii, tau = (s2 / 2, s2 / (2 dbar)).  An
+ * iteration: S = V^-1 [y, Z, U] (one batched solve of mih_grm_solve's kind, tolerance cg_tol, at most cg_max_iter iterations),
+ * Sigma = sym(Z'S_Z)^-1, P[y, U] = S - S_Z Sigma Z'S, a = Py, a second solve of [a, Phi a] and its projection; the score
+ * (a'a - t_e, a'Phi a - t_g) / 2 with t_e = mean u'Pu, t_g = mean (Phi u)'Pu; the 2 x 2 average information
+ * [a, Phi a]'[Pa, P Phi a] / 2, symmetrised; tau <- tau + 2^-h AI^-1 score with the smallest h >= 0 that keeps both components
+ * at least a tenth of their previous values; converged when 2 max |tau'_i - tau_i| / (|tau'_i| + |tau_i|) <= tol_reml.  When
+ * tau_g falls below 1e-8 s2 the fit ends on the boundary: tau_g = 0, tau_e = s2.  Then, at the final tau, alpha = Sigma Z'S_y
+ * and Py.  G (n x R, column-major, 0 <= R <= 128; NULL with R = 0): mean-imputed genotype columns for the variance ratio of
+ * GRAMMAR-Gamma / SAIGE, ratios[j] = g_j'P g_j / |(I - Z (Z'Z)^-1 Z') g_j|^2 by one more batched solve, *gamma their mean (NaN
+ * for R = 0).  Outputs: tau (2: tau_e, tau_g), alpha (c), Py (n), trace (2: the last t_e, t_g), *dbar, tau_path (2 (max_iter + 1):
+ * the start and every iterate, 2 (*iters + 1) numbers written), *iters, *state (1 converged, 2 boundary, 0 max_iter reached:
+ * no error), *cg_iters (products V P over all solves), *worst_residual (the largest |b - V x| / |b| of any solve).  The n-sized
+ * work is on the device; the c x c and 2 x 2 algebra is the host's.  The same arguments give the same bits, whatever panel_cols.
+ * Device memory: mih_grm_solve's for m = max(1 + c + probes, R) plus 8 (5 n_pad bp + (n_pad / 512 + 4) bp^2) bytes, checked
+ * before anything is allocated (MIH_OOM names both byte counts).
+ * Refusals, MIH_BAD_ARG with nothing written: everything mih_grm refuses; c < 1, probes or R out of range; n <= c; a value of
+ * y, Z or G that is not finite; a rank-deficient Z (the message names the rank); y in the span of Z; tolerances not finite
+ * or negative; max_iter or cg_max_iter < 1; a null pointer; a kinship matrix whose mean diagonal is not positive; an
+ * average-information matrix without a finite inverse. */
+int mih_lmm_null(const mih_mat *h, const uint8_t *col_keep, int method, int64_t panel_cols, const double *y, const double *Z, int32_t c,
+                 int32_t probes, uint64_t seed, const double *G, int32_t R, double tol_reml, int32_t max_iter, double cg_tol,
+                 int32_t cg_max_iter, double *tau, double *alpha, double *Py, double *gamma, double *ratios, double *trace,
+                 double *dbar, double *tau_path, int32_t *iters, int32_t *state, int64_t *cg_iters, double *worst_residual);
+/* out[i] = -log10 of the two-sided normal p-value of z[i], by the tail function every scan of this library uses (finite far
+ * beyond where p underflows; NaN for a NaN): for a caller that rescales z after a scan, as the mixed-model scan does with the
+ * variance ratio of mih_lmm_null.  Host code, no device call. */
+int mih_neglog10p(const double *z, int64_t count, double *out);
 /* The correlation of SNP pairs inside a window of columns (linkage disequilibrium) of a 2-bit handle and the pruning of its
  * columns by it, made on the device -- what `plink --indep-pairwise` does between SnpArrays.filter and the kinship matrix in
  * manuscript/NFBC_sim/NFBC_data_qc.jl:18-33; the mask goes to mih_grm / mih_grm_pairs / mih_grm_eig as col_keep.  Definitions

@@ -191,6 +191,26 @@ function assoc_sets_skato(x::HipSnpLinAlg{Float64}, A::Vector{Float64}, w::Union
             z=z, beta=beta, se=se, neglog10p=nlp)
 end
 
+# The variance-component null model of a mixed-model scan for one Normal trait (mih_lmm_null): y = Z alpha + g + e with
+# g ~ N(0, tau_g Phi), Phi the kinship matrix of the columns col_keep (nothing: all) of x, by average-information REML with
+# Hutchinson traces.  Z holds the intercept; G = mean-imputed genotype columns (n x R, R <= 128) for the variance ratio gamma.
+# The scan is then the score test with A = Py, w = nothing, and z / sqrt(gamma), beta / gamma, se / sqrt(gamma).
+function lmm_null(x::HipSnpLinAlg{Float64}, y::Vector{Float64}, Z::Matrix{Float64}, G::Matrix{Float64};
+                  col_keep::Union{Nothing, Vector{UInt8}}=nothing, method::Integer=0, panel_cols::Integer=0, probes::Integer=30,
+                  seed::Integer=0, tol::Float64=1e-5, max_iter::Integer=50, cg_tol::Float64=1e-10, cg_max_iter::Integer=500)
+    n, c, R = length(y), size(Z, 2), size(G, 2)
+    tau = zeros(2); alpha = zeros(c); Py = zeros(n); ratios = zeros(max(R, 1)); trace = zeros(2); path = fill(NaN, 2, max_iter + 1)
+    gamma = Ref(0.0); dbar = Ref(0.0); worst = Ref(0.0); iters = Ref(Int32(0)); state = Ref(Int32(0)); cg = Ref(Int64(0))
+    check(ccall((:mih_lmm_null, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{UInt8}, Cint, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Int32, UInt64, Ptr{Float64}, Int32, Float64, Int32,
+                 Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}),
+                x.handle, col_keep === nothing ? C_NULL : col_keep, method, panel_cols, y, Z, c, probes, seed, R == 0 ? C_NULL : G, R, tol, max_iter,
+                cg_tol, cg_max_iter, tau, alpha, Py, gamma, ratios, trace, dbar, path, iters, state, cg, worst))
+    return (tau=tau, alpha=alpha, Py=Py, gamma=gamma[], ratios=ratios[1:R], trace=trace, h2=tau[2] * dbar[] / (tau[2] * dbar[] + tau[1]),
+            tau_path=path[:, 1:iters[] + 1], iters=iters[], state=state[], cg_iters=cg[], worst_residual=worst[])
+end
+
 # naive_impute(x, destination) (utilities.jl:862-899) on the device copy of the genotypes
 function naive_impute(x::HipSnpLinAlg{Float64}, destination::String)
     out = Matrix{UInt8}(undef, (x.n + 3) >> 2, x.p)

@@ -170,6 +170,10 @@ _SIGNATURES = {
     "mih_grm": [_vp, _vp, C.c_int, _i64, _vp],
     "mih_grm_pairs": [_vp, _vp, C.c_int, _i64, _dbl, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp],
     "mih_grm_eig": [_vp, _vp, C.c_int, _i64, _i32, _i32, _dbl, _i32, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)],
+    "mih_grm_solve": [_vp, _vp, C.c_int, _i64, _dbl, _dbl, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _vp],
+    "mih_lmm_null": [_vp, _vp, C.c_int, _i64, _vp, _vp, _i32, _i32, C.c_uint64, _vp, _i32, _dbl, _i32, _dbl, _i32, _vp, _vp, _vp, C.POINTER(_dbl), _vp, _vp,
+                     C.POINTER(_dbl), _vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_dbl)],
+    "mih_neglog10p": [_vp, _i64, _vp],
     "mih_ld_band": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "mih_ld_pairs": [_vp, _i64, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64)],
     "mih_ld_prune": [_vp, _i64, _i64, _dbl, _i64, _i64, _vp, C.POINTER(_i64)],
@@ -448,6 +452,15 @@ def _null_scores(y, zc, d, l):
     return null, null.A, null.w, None
 
 
+def neglog10p(z):
+    """-log10 of the two-sided normal p-value of every z, by the tail function of the library's scans (mih_neglog10p): finite
+    far beyond where p underflows, NaN for a NaN."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    out = np.empty_like(z)
+    _check(lib().mih_neglog10p(_p(z), z.size, _p(out)))
+    return out
+
+
 class _Mat:
     def __init__(self):
         self._h = C.c_void_p(None)
@@ -537,15 +550,23 @@ class _Mat:
                                            *map(_p, sp.values())))
         return AssocResult(z, beta, se, nlp, beta_firth=bf, se_firth=sf, neglog10p_firth=nf, firth_state=fstate, firth_evals=fevals, **sp)
 
-    def assoc(self, y, z=None, *, d=None, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0):
+    def assoc(self, y, z=None, *, d=None, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0, kinship=None):
         """The marginal association scan: the null model y ~ z (fit_null; z=None: an intercept) and the score test of every column
         against it.  y may be n x t for Normal traits: they share the weights, and each trait's dispersion scales its own
         statistics.  Returns an AssocResult whose `null` is the NullModel (a list of them for several traits).  spa=True (one
         Bernoulli trait, logit link): the saddlepoint p-value of the columns with |z| >= spa_cutoff beside the normal one
         (score_test_spa).  firth=True (likewise): the Firth-penalised effect size and likelihood-ratio p-value of the columns with
         |z| >= firth_cutoff (score_test_firth); with spa=True too both run in one call, on one selection: spa_cutoff must then
-        equal firth_cutoff."""
+        equal firth_cutoff.
+        kinship (a SnpLinAlg or DosageMatrix, one Normal trait with the identity link, neither spa nor firth): the mixed-model
+        scan, which keeps relatives in the sample.  True fits the variance-component null model on the kinship matrix of this
+        matrix's columns (lmm_null(y, z)); an LmmNull reuses one -- the usual case, Phi from pruned markers and the scan over
+        all columns.  The scan is score_test(null.Py, None, z) as it is, then, in this order, z / sqrt(gamma), beta / gamma,
+        se / sqrt(gamma) with the variance ratio gamma of the null model (GRAMMAR-Gamma, SAIGE), and -log10 p recomputed from
+        the rescaled z (neglog10p).  `null` of the result is the LmmNull."""
         d = Normal() if d is None else _inst(d)
+        if kinship is not None and kinship is not False:
+            return self._assoc_kinship(y, z, d, l, slice_rows, spa, firth, kinship)
         opt = "firth=True" if firth else "spa=True" if spa else None
         if opt:
             if not isinstance(d, Bernoulli) or (l is not None and _inst(l).code != 1):
@@ -568,6 +589,32 @@ class _Mat:
             if y.ndim == 1:
                 null = null[0]
                 res.z, res.beta, res.se, res.neglog10p = res.z[:, 0].copy(), res.beta[:, 0].copy(), res.se[:, 0].copy(), res.neglog10p[:, 0].copy()
+        res.null = null
+        return res
+
+    def _assoc_kinship(self, y, z, d, l, slice_rows, spa, firth, kinship):
+        from .assoc import LmmNull
+        if not isinstance(self, _Kinship):
+            raise ArgumentError("kinship= needs a genotype matrix (SnpLinAlg or DosageMatrix), not a DenseMatrix")
+        if not isinstance(d, Normal) or (l is not None and _inst(l).code != 0):
+            raise ArgumentError(f"kinship= is offered for a Normal trait with the identity link only, got {type(d).__name__}"
+                                + ("" if l is None else f" with {type(_inst(l)).__name__}"))
+        if spa or firth:
+            raise ArgumentError("kinship= takes neither spa=True nor firth=True: they belong to Bernoulli traits")
+        y, zc = self._trait_args(y, z, d, "kinship=")
+        if kinship is True:
+            null = self.lmm_null(y, zc)
+        elif isinstance(kinship, LmmNull):
+            null = kinship
+            if null.Py.shape[0] != self.n:
+                raise DimensionMismatch(f"the null model has {null.Py.shape[0]} samples, expected {self.n}")
+        else:
+            raise ArgumentError(f"kinship must be True or an LmmNull, got {type(kinship).__name__}")
+        res = self.score_test(null.Py, None, zc, slice_rows)
+        res.z = res.z / np.sqrt(null.gamma)
+        res.beta = res.beta / null.gamma
+        res.se = res.se / np.sqrt(null.gamma)
+        res.neglog10p = neglog10p(res.z)
         res.null = null
         return res
 
@@ -745,6 +792,7 @@ RESERVE_BY_DEFAULT = False
 _GRM_METHODS = {"GRM": 0, "Robust": 1}
 
 PcaResult = collections.namedtuple("PcaResult", "values vectors residuals iters converged")
+SolveResult = collections.namedtuple("SolveResult", "x iters converged residuals")
 
 
 class _Kinship:
@@ -827,6 +875,79 @@ class _Kinship:
         _check(lib().mih_grm_eig(self._h, _p(ck), method, int(panel_cols), k, int(block), float(tol), int(max_iter),
                                  int(seed) & 0xFFFFFFFFFFFFFFFF, _p(values), _p(vectors), _p(residuals), C.byref(iters), C.byref(converged)))
         return PcaResult(values, vectors.T, residuals, iters.value, bool(converged.value))
+
+    def kinship_solve(self, B, tau_e, tau_g, method="GRM", minmaf=0.01, cols=None, panel_cols=0, tol=1e-10, max_iter=500):
+        """X ~ V^-1 B with V = tau_e I + tau_g Phi, Phi = grm(method, minmaf, cols): the linear solves of a mixed model on the
+        kinship matrix -- what SAIGE, fastGWA and GMMAT run inside their variance-component null model -- made on the device
+        without Phi leaving it and without an n x n factorisation (mih_grm_solve).  B: (n,) or (n, m), 1 <= m <= 128;
+        tau_e > 0, tau_g >= 0.  Returns SolveResult(x like B, iters (m,), converged (m,) bool, residuals (m,)): a conjugate
+        gradient with the Jacobi preconditioner diag V from x = 0, every column with its own scalars; column c stops when its
+        recurrence residual reaches |r|_2 <= tol |b|_2, and residuals[c] is the true |b - V x|_2, formed with one more product.
+        Reaching max_iter is not an error: converged[c] is False and the last iterate comes back with its residual.  A zero
+        column gives x = 0 after 0 iterations, converged.  A column of x is bit for bit the same whatever the other columns of
+        B, whatever panel_cols, and on a second call.  method, minmaf, cols, panel_cols: those of grm().  The device needs
+        8 n^2 bytes for the call, like grm(), plus six blocks of n x m; MemoryError names the need and what is free."""
+        method, ck = self._grm_args(method, minmaf, cols)
+        B = np.asarray(B, dtype=np.float64)
+        if B.ndim not in (1, 2) or B.shape[0] != self.n:
+            raise ArgumentError(f"B must be ({self.n},) or ({self.n}, m), got {B.shape}")
+        m = 1 if B.ndim == 1 else B.shape[1]
+        b = np.ascontiguousarray(B.reshape(self.n, m).T)                          # (m, n) row-major = n x m column-major
+        x, iters, conv, res = np.empty((max(m, 1), self.n)), np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1), dtype=np.int32), np.empty(max(m, 1))
+        _check(lib().mih_grm_solve(self._h, _p(ck), method, int(panel_cols), float(tau_e), float(tau_g), _p(b), m, float(tol), int(max_iter),
+                                   _p(x), _p(iters), _p(conv), _p(res)))
+        return SolveResult(x[0].copy() if B.ndim == 1 else np.ascontiguousarray(x.T), iters, conv.astype(bool), res)
+
+    def lmm_markers(self, markers=30, min_mac=20, seed=0):
+        """The columns whose variance ratios calibrate the mixed-model scan: among the columns with a minor-allele count of at
+        least min_mac, min(markers, their number) drawn without replacement by numpy's default_rng(seed), in ascending order."""
+        cand = np.flatnonzero(self._minor_allele_counts() >= float(min_mac))
+        if cand.size == 0:
+            raise ArgumentError(f"no column has a minor-allele count of at least {min_mac}")
+        take = min(int(markers), cand.size)
+        if take < 1 or take > 128:
+            raise ArgumentError(f"markers must be between 1 and 128, got {markers}")
+        return np.sort(np.random.default_rng(int(seed)).choice(cand, size=take, replace=False))
+
+    def lmm_null(self, y, z=None, *, method="GRM", minmaf=0.01, cols=None, panel_cols=0, probes=30, markers=30, min_mac=20, seed=0,
+                 tol=1e-5, max_iter=50, cg_tol=1e-10, cg_max_iter=500, G=None):
+        """The variance-component null model of a mixed-model association scan for one Normal trait: y = z alpha + g + e with
+        g ~ N(0, tau_g Phi), Phi = grm(method, minmaf, cols), and e ~ N(0, tau_e I), fitted on the device by average-information
+        REML with Hutchinson traces on `probes` Rademacher vectors (mih_lmm_null; the relatives stay in the sample, as in SAIGE,
+        fastGWA and GMMAT).  z: the covariates with the intercept among them, None = an intercept.  Returns an LmmNull: tau
+        (tau_e, tau_g), h2, alpha, Py (the scan's score residuals), gamma (the variance ratio that calibrates the scan) with its
+        ratios and their coefficient of variation ratio_cv, trace, tau_path (every iterate), iters, state (1 converged, 2 on the
+        boundary tau_g = 0, 0 max_iter reached: not an error), cg_iters and worst_residual (the largest relative true residual
+        of any solve).  The variance ratios are taken on the columns lmm_markers(markers, min_mac, seed), decoded on the host
+        and imputed by the mean; G (n x R, R <= 128) gives the columns instead.  tol, max_iter: of the REML iteration;
+        cg_tol, cg_max_iter: of its solves (kinship_solve).  The same arguments give the same bits, whatever panel_cols.  Usually
+        Phi comes from pruned markers and the scan runs over all: null = x.lmm_null(y, z, cols=pruned); x.assoc(y, z, kinship=null)."""
+        from .assoc import LmmNull
+        method, ck = self._grm_args(method, minmaf, cols)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim != 1:
+            raise ArgumentError("lmm_null takes one trait")
+        if y.shape[0] != self.n:
+            raise DimensionMismatch(f"y has {y.shape[0]} rows, expected {self.n}")
+        zc = np.ones((self.n, 1)) if z is None else np.asarray(z, dtype=np.float64).reshape(self.n, -1)
+        if G is None:
+            marker_cols = self.lmm_markers(markers, min_mac, seed)
+            G = self._marker_genotypes(marker_cols)
+        else:
+            marker_cols, G = None, np.asarray(G, dtype=np.float64).reshape(self.n, -1)
+        c, R, probes, max_iter = zc.shape[1], G.shape[1], int(probes), int(max_iter)
+        if max_iter < 1:
+            raise ArgumentError(f"max_iter must be at least 1, got {max_iter}")
+        zf, gf = np.ascontiguousarray(zc.T), np.ascontiguousarray(G.T)          # column-major
+        tau, alpha, py, ratios, trace = np.empty(2), np.empty(max(c, 1)), np.empty(self.n), np.empty(max(R, 1)), np.empty(2)
+        path = np.full((max_iter + 1, 2), np.nan)
+        gamma, dbar, worst = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        iters, state, cg = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        _check(lib().mih_lmm_null(self._h, _p(ck), method, int(panel_cols), _p(y), _p(zf), c, probes, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  _p(gf), R, float(tol), max_iter, float(cg_tol), int(cg_max_iter), _p(tau), _p(alpha), _p(py), C.byref(gamma),
+                                  _p(ratios), _p(trace), C.byref(dbar), _p(path), C.byref(iters), C.byref(state), C.byref(cg), C.byref(worst)))
+        return LmmNull(tau, alpha[:c], py, gamma.value, ratios[:R], trace, dbar.value, path[:iters.value + 1], iters.value, state.value,
+                       cg.value, worst.value, marker_cols, zc)
 
 
 class SnpLinAlg(_Mat, _Kinship):
@@ -946,6 +1067,19 @@ class SnpLinAlg(_Mat, _Kinship):
 
     def _allele_maf(self):
         return self.maf()
+
+    def _minor_allele_counts(self):
+        cnt = self.counts()[0].astype(np.float64)
+        return np.minimum(cnt[:, 1] + 2.0 * cnt[:, 2], cnt[:, 1] + 2.0 * cnt[:, 0])
+
+    def _marker_genotypes(self, cols):
+        """The allele counts of a few columns (n x len(cols)), decoded on the host, a missing one imputed by the column's mean."""
+        bed = self.subset(cols=cols).export_bed()
+        two = np.stack([(bed >> s) & 3 for s in (0, 2, 4, 6)], axis=2).reshape(bed.shape[0], -1)[:, :self.n]
+        g = np.array([0.0, np.nan, 1.0, 2.0])[two].T
+        with np.errstate(invalid="ignore"):
+            mean = np.nanmean(g, axis=0)
+        return np.where(np.isnan(g), np.where(np.isnan(mean), 0.0, mean)[None, :], g)
 
     def missing_rate(self, axis):
         """The share of missing genotypes per column (axis = 0: over the rows, length p) or per row (axis = 1, length n)."""
@@ -1304,6 +1438,17 @@ class DosageMatrix(_Mat, _Kinship):
     def _allele_maf(self):
         f = self.mu_sigma()[0] / 2.0
         return np.minimum(f, 1.0 - f)
+
+    def _minor_allele_counts(self):
+        return 2.0 * self.n * self._allele_maf()                     # (expected counts: dosages are not integers)
+
+    def _marker_genotypes(self, cols):
+        """The dosages of a few columns (n x len(cols)), decoded on the host, a missing one imputed by the column's mean."""
+        g = np.column_stack([self.export(int(j), 1)[:, 0] for j in cols]).astype(np.float64)
+        g = np.where(g == 0xFFFF, np.nan, g / float(self.denom))
+        with np.errstate(invalid="ignore"):
+            mean = np.nanmean(g, axis=0)
+        return np.where(np.isnan(g), np.where(np.isnan(mean), 0.0, mean)[None, :], g)
 
     def regrid(self, denom):
         """The same matrix over the finer grid 1 / denom (a multiple of self.denom, at most 32767): every numerator times
@@ -2167,18 +2312,21 @@ def iht(plinkfile, k, d, *, phenotypes=6, covariates="", summaryfile="iht.summar
 
 
 def gwas(plinkfile, d, *, phenotypes=6, covariates="", outfile="gwas.txt", exclude_std_idx=(), dosage=False, device=0,
-         two_bit=False, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0):
+         two_bit=False, l=None, slice_rows=0, spa=False, spa_cutoff=2.0, firth=False, firth_cutoff=2.0, lmm=False):
     """The single-SNP association scan of a file, beside iht(): the inputs are parsed as iht parses them, the null model of the
     covariates is fitted (fit_null) and every SNP gets its score test (x.assoc).  outfile: `chr pos SNPid ref alt z beta se
     neglog10p`, one row per SNP, tab-separated; spa=True (Bernoulli, logit link) adds the columns `neglog10p_spa spa_state`,
-    firth=True (likewise) appends `beta_firth se_firth neglog10p_firth firth_state`.  Returns the AssocResult."""
+    firth=True (likewise) appends `beta_firth se_firth neglog10p_firth firth_state`.  lmm=True (a Normal trait): the mixed-model
+    scan on the kinship matrix of the file's own SNPs, which keeps relatives in the sample (x.assoc(kinship=True)); the columns
+    are the same, `null` of the result is the LmmNull.  Returns the AssocResult."""
     d = _inst(d)
     x, y, z, info = _parse_inputs(plinkfile, phenotypes, covariates, d, exclude_std_idx, dosage, device, two_bit)
     if _is_multivariate(y):
         raise ArgumentError("gwas scans one phenotype at a time")
     if l is None:
         l = LogLink() if isinstance(d, NegativeBinomial) else canonicallink(d)
-    res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=bool(spa), spa_cutoff=spa_cutoff, firth=bool(firth), firth_cutoff=firth_cutoff)
+    res = x.assoc(y, z, d=d, l=l, slice_rows=slice_rows, spa=bool(spa), spa_cutoff=spa_cutoff, firth=bool(firth), firth_cutoff=firth_cutoff,
+                  kinship=True if lmm else None)
     if outfile:
         chrom, pos, ids, a1, a2 = info
         with open(outfile, "w") as f:

@@ -145,6 +145,30 @@ def fit_null(y, z, d, l=None, tol=1e-8, max_iter=100, est_r="None"):
     return NullModel(gamma, eta, mu, phi, A, w, dev, iters, converged)
 
 
+class LmmNull:
+    """The fitted variance-component null model y = Z alpha + g + e, g ~ N(0, tau_g Phi), e ~ N(0, tau_e I) (lmm_null of
+    SnpLinAlg and DosageMatrix): tau = (tau_e, tau_g), h2 = tau_g dbar / (tau_g dbar + tau_e) with dbar the mean diagonal of
+    Phi, alpha, Py (what the score test takes as A), gamma -- the mean of the variance ratios `ratios` of the marker columns
+    `marker_cols` (None when the caller gave the genotypes), ratio_cv their coefficient of variation -- trace (the last
+    Hutchinson estimates of tr P and tr P Phi), tau_path (the start and every iterate), iters, state (1 converged, 2 on the
+    boundary tau_g = 0, 0 max_iter reached), cg_iters, worst_residual, and the covariates Z the model was fitted with."""
+    def __init__(self, tau, alpha, Py, gamma, ratios, trace, dbar, tau_path, iters, state, cg_iters, worst_residual, marker_cols, Z):
+        self.tau, self.alpha, self.Py, self.gamma, self.ratios, self.trace, self.dbar = tau, alpha, Py, gamma, ratios, trace, dbar
+        self.tau_path, self.iters, self.state, self.cg_iters, self.worst_residual = tau_path, iters, state, cg_iters, worst_residual
+        self.marker_cols, self.Z = marker_cols, Z
+        self.h2 = float(tau[1] * dbar / (tau[1] * dbar + tau[0]))
+        m = float(np.mean(ratios)) if len(ratios) else float("nan")
+        self.ratio_cv = float(np.std(ratios) / m) if len(ratios) else float("nan")
+
+    @property
+    def converged(self):
+        return self.state != 0
+
+    def __repr__(self):
+        return (f"LmmNull(tau_e={self.tau[0]!r}, tau_g={self.tau[1]!r}, h2={self.h2!r}, gamma={self.gamma!r}, iters={self.iters}, "
+                f"state={self.state})")
+
+
 class AssocResult:
     """z, beta, neglog10p: p (one trait) or p x t; se likewise.  NaN marks a degenerate column.  null: the NullModel (a list of
     them for several Normal traits).  With the saddlepoint pass (score_test_spa, assoc(..., spa=True)): neglog10p_spa (p),
